@@ -5,11 +5,18 @@ One step = one full training update on one max-tokens-40000 batch per rank: GPU 
 -> 6-layer unit decoder -> label-smoothed CE -> hand-written backward with bucketed RCCL all-reduce
 -> FP16Optimizer/Adam.  Synthetic Speech-Multi30K-shaped data, random-init weights.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line (value = frames processed by all ranks / max-over-ranks wall time).
+
+A plain run does what the headline figure needs and no more: set-up, loss-scale settling, W warm-up
+steps, the K timed steps, the outputs of the last timed step if --dump-outputs is given, the line.
+--full adds the measurements that take passes of their own: the one-step-at-a-time host issue
+cost, the serial roofline pass over the GEMM kernels (the line's "roofline" block), the fp32
+master checksum / rank-identity check and the CPU baseline (--no-gemm-timing / --no-cpu-baseline
+leave the two long legs out of a --full run).
 """
 import argparse
 import importlib
@@ -236,7 +243,7 @@ def decode_main(args):
     N, H, hd = bsz * beam, cfg["decoder_attention_heads"], cfg["decoder_embed_dim"] // cfg["decoder_attention_heads"]
     # decode self-attention: every cached K and V row of every hypothesis read once per layer-step
     attn_bytes = sum(N * H * t * hd * 2 * 2 for t in range(1, steps + 1)) * cfg["decoder_layers"]
-    cpu = None if args.no_cpu_baseline else decode_cpu_baseline(model, sample, beam, args.cpu_budget)
+    cpu = decode_cpu_baseline(model, sample, beam, args.cpu_budget) if args.full and not args.no_cpu_baseline else None
     print(json.dumps({
         "metric": "beam-search decode hypothesis-tokens/s (fairseq-generate --beam 10 --max-len-a 1)",
         "value": steps * N / dt, "unit": "hypothesis-tokens/s", "n_gpus": 1, "steps": steps,
@@ -300,6 +307,53 @@ def host_issue_cost(step, base, n, world):
     return 1e3 * cpu / max(n, 1)
 
 
+DUMP_BUDGET = 64 * 2 ** 20      # bytes of .npy data one --dump-outputs run may write
+DUMP_SAMPLE = 2_000_000         # elements kept of each flat parameter-sized buffer
+DUMP_SRC_MAX = 4_000_000        # elements kept of the step's feature tensor
+
+
+def dump_outputs(out_dir, tr, log, wb, batch):
+    """--dump-outputs: what the last timed step handed back to its caller, as float32 .npy files.
+
+      log.npy             the step log train_step returns: loss, nll, ntokens, nsentences, ntokens/world
+      src.npy             the fbank + CMVN features the step's prologue produced [B, Tmax, 80], padding
+                          frames zeroed (flattened and sampled like the buffers below past DUMP_SRC_MAX)
+      ost.npy             the optimizer's device state vector (grad norm, loss scale, step, lr, ...)
+      params_sample.npy   the updated fp16 parameters            \\  the same DUMP_SAMPLE sorted flat
+      master_sample.npy   their fp32 master copy                  | indices of each buffer, drawn once
+      exp_avg_sample.npy, exp_avg_sq_sample.npy  the Adam moments /  from numpy default_rng(0)
+
+    The moments carry the step's gradients (exp_avg moves by 0.1 x grad per update) where the
+    learning-rate warm-up keeps the parameter change itself small."""
+    os.makedirs(out_dir, exist_ok=True)
+    tr.sync()
+    torch.cuda.synchronize()
+
+    def sample(t, n):
+        t = t.detach().reshape(-1)
+        if t.numel() > n:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), n))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.float().cpu().numpy()
+
+    src = batch.src.detach().float()
+    pad = torch.arange(src.shape[1], device=src.device)[None, :] >= wb["n_frames"].to(src.device)[:, None]
+    src = src.masked_fill(pad[:, :, None], 0.0)
+    opt = tr.opt
+    arrays = {"log": log.detach().float().cpu().numpy(),
+              "src": src.cpu().numpy() if src.numel() <= DUMP_SRC_MAX else sample(src, DUMP_SRC_MAX),
+              "ost": opt.ost.detach().float().cpu().numpy(),
+              "params_sample": sample(tr.model.params.flat, DUMP_SAMPLE),
+              "master_sample": sample(opt.master, DUMP_SAMPLE),
+              "exp_avg_sample": sample(opt.exp_avg, DUMP_SAMPLE),
+              "exp_avg_sq_sample": sample(opt.exp_avg_sq, DUMP_SAMPLE)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes (limit {DUMP_BUDGET})")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -316,8 +370,13 @@ def main():
                     help="replay each training step as a captured HIP graph (world size 1).  Off by "
                          "default: ROCm 7 executes the captured step without the weight-gradient "
                          "side stream's overlap (22.6 ms vs 18.3 ms eager, DESIGN.md §7)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gemm-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: host issue cost, the serial GEMM "
+                         "roofline pass, master checksum / rank identity, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gemm-timing", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--decode", action="store_true", help="beam-search inference line instead of training")
     ap.add_argument("--decode-bsz", type=int, default=16)
@@ -332,6 +391,7 @@ def main():
         world = dist.get_world_size()          # n_gpus as the process group sees it
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
+    np.random.seed(1 + rank)   # the model's modality-dropout draws (numpy's global stream): same run to run
     detr = args.image_feats == "detr"
     img_tokens = 100 if detr else 577
     cfg = mm.default_cfg(fusion=not args.audio_only, **(dict(image_feat_dim=256, SA_image_dropout=0.5,
@@ -349,7 +409,7 @@ def main():
 
         def frontend():     # GPU fbank + CMVN of the resident waveforms, part of the step
             batch.src = fe(wb)
-        tr.train_step(batch, prologue=frontend, eager=eager, draws=draws)
+        return tr.train_step(batch, prologue=frontend, eager=eager, draws=draws)
 
     # untimed loss-scale settling: the fp16 optimizer starts at scale 128 (fairseq --fp16-init-scale)
     # and skips the update of every overflowing step while it halves the scale; run until a step
@@ -379,6 +439,7 @@ def main():
         n_graphs = len(tr.graphs)
     base = args.warmup   # the timed batch sequence does not depend on how many settling steps ran
     host_cpu = [0.0]   # CPU seconds of the issuing threads (main + autograd backward) in the last window
+    last_log = [None]  # what the window's last train_step returned (--dump-outputs)
 
     def timed(profile):
         """K steps between barrier + synchronize on both sides -> (seconds, host issue seconds, GEMM stats).
@@ -411,7 +472,7 @@ def main():
         c0, b0 = time.thread_time(), runtime.BWD_CPU_S[0]
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(base + i, eager=profile)
+            last_log[0] = step(base + i, eager=profile)
         t_issue = time.perf_counter()  # host finished enqueueing (host-bound if ~ t1)
         host_cpu[0] = time.thread_time() - c0 + runtime.BWD_CPU_S[0] - b0
         if prof is not None:
@@ -439,15 +500,21 @@ def main():
             kernels._Side.enabled = side_was
         return t1 - t0, t_issue - t0, g, launches
 
-    # the throughput region runs uninstrumented; the same K steps are then re-run serially with the
-    # library's in-kernel workgroup stamps for the roofline
+    # the throughput region runs uninstrumented; --full then re-runs the same K steps serially with
+    # the library's in-kernel workgroup stamps for the roofline
     t_run, t_issue_run, _, _ = timed(False)
     host_cpu_run = host_cpu[0]
-    host_cost = host_issue_cost(step, base, min(args.steps, 5), world)
+    if args.dump_outputs and rank == 0:
+        # before any further step runs: the state the last timed step left
+        wb_last, batch_last = batches[(base + args.steps - 1) % len(batches)][:2]
+        dump_outputs(args.dump_outputs, tr, last_log[0], wb_last, batch_last)
+    if world > 1 and args.dump_outputs:
+        dist.barrier()
+    host_cost = host_issue_cost(step, base, min(args.steps, 5), world) if args.full else None
     t_prof = None
     gemm_ms, n_launch, launched_flops, gemm_bytes = 0.0, 0, 0.0, 0.0
     classes, templates = {}, {}
-    if not args.no_gemm_timing:
+    if args.full and not args.no_gemm_timing:
         t_prof, _, (gemm_ms, n_launch, launched_flops, gemm_bytes), (l_ms, l_fl, l_cls) = timed(True)
         if os.environ.get("MMS2UT_GEMM_DUMP"):
             # per-launch table of the roofline pass (scripts/gemm_table.py summarises it)
@@ -493,13 +560,40 @@ def main():
     ost = dict(tr.opt.stats(), untimed_scale_settling_steps=settle)
     # fp32 master checksum after every step above: equal on all ranks (DP keeps replicas identical)
     # and, for a fixed step sequence, independent of --bucket-mb (scripts/_dp2_rehearsal.sh)
-    tr.sync()
-    ck = torch.tensor([float(tr.opt.master.double().sum())], dtype=torch.float64, device=device)
-    ost["master_checksum"] = float(ck)
-    if world > 1:
-        cks = [torch.zeros_like(ck) for _ in range(world)]
-        dist.all_gather(cks, ck)
-        ost["ranks_identical"] = all(float(c) == float(ck) for c in cks)
+    if args.full:
+        tr.sync()
+        ck = torch.tensor([float(tr.opt.master.double().sum())], dtype=torch.float64, device=device)
+        ost["master_checksum"] = float(ck)
+        if world > 1:
+            cks = [torch.zeros_like(ck) for _ in range(world)]
+            dist.all_gather(cks, ck)
+            ost["ranks_identical"] = all(float(c) == float(ck) for c in cks)
+    line = {
+        "metric": "audio-frames/sec/node, mm_s2ut_transformer fp16, max-tokens 40000, 1/2/4/8 GPUs",
+        "value": frames_all / elapsed,
+        "unit": "audio-frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "fp16", "data": "synthetic (Speech-Multi30K-shaped; random-init weights)",
+        "config": {"workload": ("mm_s2ut_transformer base audio-only" if args.audio_only else
+                                "mm_s2ut_transformer base (DETR-256 x 100 image feats, SA_image_dropout 0.5, "
+                                "modality/audio dropout 0.5)" if detr else
+                                "mm_s2ut_transformer base (ViT-768 image feats, multimodal_attention+gate)"),
+                   "model": "mm_s2ut_transformer", "max_tokens": args.max_tokens,
+                   "global_batch_frames_per_step": frames_all / args.steps,
+                   "parallelism": f"dp{world}", "front_end": "GPU fbank+CMVN in step",
+                   "alg_flops_per_frame": total_flops_all / max(frames_all, 1),
+                   "model_tflops_per_s": total_flops_all / elapsed / 1e12},
+    }
+    if not args.full:
+        # the plain run ends here: the headline figure, its configuration and the optimizer's state
+        if rank == 0:
+            print(json.dumps(dict(line, optimizer=ost)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     traffic, traffic_src = gemm_pmc_traffic()
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -519,22 +613,7 @@ def main():
                           "frac": v[1] / max(v[0], 1e-9) / 1e9 / MFMA_PEAK_F16}
                       for k, v in sorted(templates.items(), key=lambda kv: -kv[1][0])}
         line = {
-            "metric": "audio-frames/sec/node, mm_s2ut_transformer fp16, max-tokens 40000, 1/2/4/8 GPUs",
-            "value": frames_all / elapsed,
-            "unit": "audio-frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "fp16", "data": "synthetic (Speech-Multi30K-shaped; random-init weights)",
-            "config": {"workload": ("mm_s2ut_transformer base audio-only" if args.audio_only else
-                                    "mm_s2ut_transformer base (DETR-256 x 100 image feats, SA_image_dropout 0.5, "
-                                    "modality/audio dropout 0.5)" if detr else
-                                    "mm_s2ut_transformer base (ViT-768 image feats, multimodal_attention+gate)"),
-                       "model": "mm_s2ut_transformer", "max_tokens": args.max_tokens,
-                       "global_batch_frames_per_step": frames_all / args.steps,
-                       "parallelism": f"dp{world}", "front_end": "GPU fbank+CMVN in step",
-                       "alg_flops_per_frame": total_flops_all / max(frames_all, 1),
-                       "model_tflops_per_s": total_flops_all / elapsed / 1e12},
+            **line,
             "roofline": {"bound": "mfma", "kernel": "mms2ut GEMM family (gemm_dma / gemm256p, all launches)",
                          "achieved": achieved, "peak": MFMA_PEAK_F16, "unit": "TFLOP/s",
                          "frac": (achieved / MFMA_PEAK_F16) if achieved else None, "traffic": traffic,

@@ -11,7 +11,7 @@ out=${1:-gpurun_out/dp2}
 mkdir -p "$out"
 export MMS2UT_DIST_BACKEND=gloo
 for mb in 8 25 64 128; do
-  timeout -k 10 300 python -u bench.py --gpus 2 --steps 4 --warmup 2 --no-cpu-baseline --no-gemm-timing \
+  timeout -k 10 300 python -u bench.py --gpus 2 --steps 4 --warmup 2 --full --no-cpu-baseline --no-gemm-timing \
     --bucket-mb $mb > "$out/bucket_$mb.json" 2> "$out/bucket_$mb.err"
   tail -1 "$out/bucket_$mb.json"
 done

@@ -1,6 +1,6 @@
 """In-step vs isolated GEMM time per launch shape.
 
-Reads a roofline-pass dump of bench.py (MMS2UT_GEMM_DUMP=path.npz) and re-times every distinct
+Reads a roofline-pass dump of bench.py --full (MMS2UT_GEMM_DUMP=path.npz) and re-times every distinct
 (A/B layout, M, N, K, split, epilogue) isolated and warm (random operands, 20 back-to-back calls,
 plain fp16 / fp32-slab epilogue), so the table separates what the shape costs from what the step
 adds (cold operands, fused epilogues, stream contention).

@@ -1,4 +1,4 @@
-"""Summarise a bench roofline-pass GEMM dump (MMS2UT_GEMM_DUMP=path.npz python bench.py ...):
+"""Summarise a bench roofline-pass GEMM dump (MMS2UT_GEMM_DUMP=path.npz python bench.py --full ...):
 per (class, M-bucket, N, K, epilogue) the launches per step, time per step and TF/s.
 
     python scripts/gemm_table.py path.npz

@@ -29,11 +29,11 @@ for s in "$@"; do
   case $s in
     tests) run tests 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ;;
     smoke) run smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python bench.py ;;
-    bench_audio) run bench_audio 300 python bench.py --audio-only --no-cpu-baseline ;;
-    bench_detr) run bench_detr 300 python bench.py --image-feats detr --no-cpu-baseline ;;
+    bench) run bench 300 python bench.py --full ;;
+    bench_audio) run bench_audio 300 python bench.py --full --audio-only --no-cpu-baseline ;;
+    bench_detr) run bench_detr 300 python bench.py --full --image-feats detr --no-cpu-baseline ;;
     trace) run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- \
-             python bench.py --steps 6 --warmup 3 --no-cpu-baseline ;;
+             python bench.py --full --steps 6 --warmup 3 --no-cpu-baseline ;;
     traffic)
       run pmc_fetch 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch" -o run -- python $B
       run pmc_write 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/pmc_write" -o run -- python $B

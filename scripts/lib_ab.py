@@ -23,7 +23,7 @@ for rep in range(reps):
             res.setdefault(name, {})["ops"] = ln
             print(name, *ln, sep="\n  ", flush=True)
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
-                            "--no-cpu-baseline", "--no-gemm-timing"], env=env, capture_output=True, text=True,
+                            "--full", "--no-cpu-baseline", "--no-gemm-timing"], env=env, capture_output=True, text=True,
                            timeout=300, cwd=ROOT)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if p.returncode or not line:

@@ -1,8 +1,8 @@
 """Idle time of a rocprofv3 kernel trace of bench.py: per optimizer step, the wall time, the summed
 kernel time, the time some kernel is running on any queue (busy), and the largest idle gaps with
 the kernels on either side.  usage: python scripts/trace_gaps.py run_kernel_trace.csv [N] [SKIP] [TOP]
-(N steps ending SKIP steps before the last fbank launch; bench.py's serial roofline pass follows
-its timed pass, so SKIP = N selects the timed pass)."""
+(N steps ending SKIP steps before the last fbank launch; bench.py --full's serial roofline pass
+follows its timed pass, so SKIP = N selects the timed pass there)."""
 import csv
 import re
 import sys

@@ -1,6 +1,6 @@
 """Per-kernel totals over the last N optimizer steps of a rocprofv3 kernel trace of bench.py, split
 by queue (main vs side stream).  usage: python scripts/trace_totals.py run_kernel_trace.csv [N] [SKIP]
-SKIP: leave out the last SKIP steps (bench.py's serial roofline pass follows its timed pass)."""
+SKIP: leave out the last SKIP steps (bench.py --full's serial roofline pass follows its timed pass)."""
 import csv
 import re
 import sys

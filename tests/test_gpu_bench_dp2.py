@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 def _run(bucket_mb):
     env = dict(os.environ, MMS2UT_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-gemm-timing", "--bucket-mb", str(bucket_mb)]
+           "--full", "--no-cpu-baseline", "--no-gemm-timing", "--bucket-mb", str(bucket_mb)]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=420)
     out = p.stdout.decode(errors="replace")
     assert p.returncode == 0, out[-3000:]

@@ -235,8 +235,10 @@ def test_fairseq_dropin_task_dataset_model_cpu(monkeypatch, tmp_path):
 
 def _reducer_worker(rank, world, port, q):
     import os
+    # MMS2UT_DIST_BACKEND=gloo: a host-tensor rehearsal, so on a machine with fewer GPUs than ranks the
+    # ranks share devices (parallel.init_from_env) instead of rank 1 refusing to start
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MMS2UT_DIST_BACKEND="gloo")
     try:
         par = pkg("parallel")
         r, w, _ = par.init_from_env(backend="gloo")
@@ -272,9 +274,15 @@ def test_grad_allreducer_gloo_world2():
     ps = [ctx.Process(target=_reducer_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in ps:
         p.start()
-    res = sorted(q.get(timeout=120) for _ in ps)
-    for p in ps:
-        p.join(timeout=60)
+    try:
+        res = sorted(q.get(timeout=120) for _ in ps)
+        for p in ps:
+            p.join(timeout=60)
+    finally:
+        for p in ps:        # a rank still waiting for a peer that failed must not outlive the test
+            if p.is_alive():
+                p.terminate()
+                p.join(timeout=10)
     for r, launched, ok, scal in res:
         assert launched == 4, (r, launched, ok)  # every bucket launched during the "backward"
         assert ok is True
