@@ -513,6 +513,30 @@ int mms2ut_fbank_cmvn_collate(const float* feats, const int32_t* frame_off, int 
 int mms2ut_specaugment_f16(mms2ut_half* x, const int32_t* frame_off, int B, int Tmax, int nbins,
                            const int32_t* masks, int n_freq, int n_time, int use_const,
                            float mask_value, hipStream_t stream);
+/* Noise augmentation (--noise-config-yaml): the reference's select_noise + add_noise_v2
+ * (audio_utils.py:27-42, :161-233 with noise_waveform_start=-1, add_white_noise=False,
+ * normalize=True; called per utterance on the CPU by speech_to_speech_dataset.py:217-240), in
+ * place on the wave batch in front of mms2ut_fbank_f32.  bank: the noise clips' int16 samples back
+ * to back, bank_off[n_clips + 1].  params: [B][3 + n_mix] int32 rows {apply, start, f, clip ids}:
+ * apply 0 leaves the utterance's samples bit-untouched; start is the crop start into the tiled
+ * noise (the noise sample of utterance sample t is n[(start + t) mod L], L = the shortest chosen
+ * clip); f is the bit pattern of the fp32 factor 1 / (10^(SNR/20) + 1), computed on the host (no
+ * pow on the device).  n_mix > 1: the noise is floor(mean of the clips), i.e. -1 where the integer
+ * sum of the int16 samples is negative and 0 elsewhere.  With x = wave * 2^-15, every
+ * operation rounded to fp32 on its own (no FMA), sums exact in fp64:
+ *   clean_amp = sum|x| / T; noise_amp = sum|seg| / T; g = f * clean_amp / (noise_amp + 1e-14);
+ *   y = x * (1 - f) + seg * g; wave = y / max(max|y|, 1) * 2^15.
+ * Three launches over grid (B, MMS_NOISE_SPLIT), deterministic (no atomics); an utterance's
+ * result does not depend on its offset in the batch.  The kernels never read outside a clip for
+ * any params row (rows with a clip id out of range or an empty clip are skipped); the caller
+ * validates ids, 0 <= start and start + T <= ceil(T / L) * L.
+ * ws: caller-owned workspace of MMS_NOISE_WS_DOUBLES(B) doubles.                                */
+#define MMS_NOISE_SPLIT    8
+#define MMS_NOISE_MAX_MIX  4
+#define MMS_NOISE_WS_DOUBLES(B) ((int64_t)3 * (B) * MMS_NOISE_SPLIT)
+int mms2ut_noise_mix_f32(float* wave, const int64_t* wave_off, int B,
+                         const int16_t* bank, const int64_t* bank_off, int n_clips,
+                         const int32_t* params, int n_mix, double* ws, hipStream_t stream);
 
 /* ---------------------------------------------------------------- transformer layers
  * One whole pre-LN transformer layer per call — SURVEY §8b "encoder / decoder layer fwd/bwd":

@@ -211,6 +211,7 @@ SIGNATURES = {
     "mms2ut_fbank_f32": (i32, [vp, vp, vp, i32, i32, vp, vp, i32, vp, vp]),
     "mms2ut_fbank_cmvn_collate": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "mms2ut_specaugment_f16": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, vp]),
+    "mms2ut_noise_mix_f32": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]),
     "mms2ut_layer_arena": (i32, [vp, vp, vp]),
     "mms2ut_layer_scratch": (i32, [vp, f32, vp, vp]),
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),

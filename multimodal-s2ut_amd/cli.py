@@ -129,7 +129,8 @@ def _manifest_epochs(args, task, cfg, fus, rank, world, dev):
                                  data_cfg=data_cfg, image_feat_path=feat,
                                  max_source_positions=cfg.get("max_source_positions", 6000),
                                  max_target_positions=cfg.get("max_target_positions", 1024),
-                                 multitask=getattr(task, "multitask_tasks", None))
+                                 multitask=getattr(task, "multitask_tasks", None),
+                                 noise=getattr(task, "noise", None))
     uf = args.update_freq
 
     def epoch_updates(epoch, skip):

@@ -183,6 +183,12 @@ def register(fairseq):
         def __init__(self, man, seed=1, epoch=1):
             super().__init__()
             self.man, self.seed, self.epoch = man, seed, epoch
+            # registered before the DataLoader workers fork: they draw from the clip lengths, this
+            # process keeps the bank for the model's forward (frontend.wave_net_input_src)
+            self.noise_key = None
+            if man.noise is not None:
+                from .frontend import register_noise_bank
+                self.noise_key = register_noise_bank(man.noise.key, man.noise)
 
         def __len__(self):
             return len(self.man)
@@ -205,9 +211,14 @@ def register(fairseq):
             ni["src_waves"] = torch.cat(waves)
             ni["src_wave_offsets"] = torch.from_numpy(off)
             ni["src_cmvn"] = bool(self.man.cmvn)
-            sa = self.man.specaugment
-            if sa is not None and sa.fn + sa.tn > 0:
+            sa, nz = self.man.specaugment, self.man.noise
+            sa = sa if sa is not None and sa.fn + sa.tn > 0 else None
+            if sa is not None or nz is not None:
                 rng = np.random.RandomState((self.seed * 1000003 + self.epoch * 7919 + order[0]) % 2 ** 32)
+            if nz is not None:          # noise draws first, then SpecAugment's, from the one stream
+                ni["src_noise"] = {"params": torch.from_numpy(nz.draws([w.numel() for w in waves], rng)),
+                                   "n_mix": nz.noise_num, "bank": self.noise_key}
+            if sa is not None:
                 ni["src_specaugment"] = {"masks": torch.from_numpy(sa.draws(sample["net_input"]["src_lengths"].tolist(),
                                                                            80, rng)),
                                          "n_freq": sa.fn, "n_time": sa.tn, "mask_value": sa.mask_value}

@@ -1209,6 +1209,28 @@ def specaugment(x, frame_off, masks, n_freq, n_time, mask_value=None):
     return x
 
 
+NOISE_SPLIT, NOISE_MAX_MIX = 8, 4   # include/mms2ut.h MMS_NOISE_SPLIT, MMS_NOISE_MAX_MIX
+
+
+def noise_mix(wb, bank, bank_off, params, n_mix):
+    """Noise augmentation in place on the wave batch ``wb`` (FbankFrontend.upload / from_device):
+    bank int16 [N] + bank_off int64 [n_clips + 1] and params int32 [B, 3 + n_mix] on the wave's
+    device (see include/mms2ut.h; the caller has validated params, frontend.NoiseAugment.check)."""
+    wave, B = wb["wave"], wb["B"]
+    if not 1 <= n_mix <= NOISE_MAX_MIX:
+        raise ValueError(f"noise_mix: n_mix {n_mix} (1 .. {NOISE_MAX_MIX})")
+    if params.shape != (B, 3 + n_mix) or params.dtype != torch.int32 or params.device != wave.device \
+            or not params.is_contiguous():
+        raise ValueError(f"noise_mix: params {tuple(params.shape)} {params.dtype} for B={B}, n_mix={n_mix}")
+    if bank.dtype != torch.int16 or bank_off.dtype != torch.int64 or bank.device != wave.device \
+            or bank_off.device != wave.device or wave.dtype != torch.float32:
+        raise ValueError("noise_mix: int16 bank, int64 offsets and fp32 wave on one device expected")
+    ws = torch.empty(3 * B * NOISE_SPLIT, dtype=torch.float64, device=wave.device)   # MMS_NOISE_WS_DOUBLES
+    call("mms2ut_noise_mix_f32", wave.data_ptr(), wb["wave_off"].data_ptr(), B, bank.data_ptr(),
+         bank_off.data_ptr(), bank_off.numel() - 1, params.data_ptr(), int(n_mix), ws.data_ptr(), _s())
+    return wave
+
+
 def log_softmax_step(logits, V, pad, eos, mode=0, out=None):
     """fp32 [rows, V] = log_softmax(logits[:, :V].float()) with the beam-search step masks
     (mode 0: pad; 1: force eos; 2: forbid eos)."""

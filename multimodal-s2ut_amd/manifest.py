@@ -9,7 +9,8 @@ What the reference does per utterance on the CPU, in DataLoader workers
     (+ optional ``{split}_mask.pth``) per ``image_feat_path`` entry (:606-616, ``ImageDataset`` :36-68).
   * ``get_source_audio`` :234-274 — ``sf.read(float32)`` then ``get_features_or_waveform`` ->
     ``get_fbank`` (audio_utils.py:326-349): mono, ×2^15, Kaldi fbank; then the data config's
-    feature transforms (utterance CMVN).
+    feature transforms (utterance CMVN).  With ``--noise-config-yaml``, ``add_noise`` :217-232
+    mixes a noise clip into the waveform first (here: frontend.NoiseAugment, on the GPU).
   * ``__getitem__`` :276-342 — target = ``tgt_dict.encode_line(tgt_text, append_eos=True)``;
     image row = int(stem of the audio file name) - 1 (:319-320).
   * ``collater`` :377-471 (restated in ``data.collater``).
@@ -95,6 +96,12 @@ def read_wav(path):
     ``sf.read(dtype="float32")`` (x / 2^15) followed by ``get_waveform(normalization=False)``'s
     × 2^15, which round-trips int16 exactly.  Multi-channel input is averaged to mono (sox
     ``channels 1``, as fairseq ``convert_waveform(to_mono=True)``)."""
+    x, sr, _ = read_wav_info(path)
+    return x, sr
+
+
+def read_wav_info(path):
+    """``read_wav`` plus the file's channel count -> (samples, sample rate, channels)."""
     with wave.open(path, "rb") as w:
         if w.getsampwidth() != 2:
             raise ValueError(f"{path}: only 16-bit PCM WAV is supported (got {8 * w.getsampwidth()}-bit)")
@@ -103,7 +110,7 @@ def read_wav(path):
     x = np.frombuffer(raw, dtype="<i2").astype(np.float32)
     if ch > 1:
         x = x.reshape(-1, ch).mean(axis=1, dtype=np.float32)
-    return x, sr
+    return x, sr, ch
 
 
 def write_wav(path, samples, sample_rate=16000):
@@ -149,6 +156,17 @@ def load_data_config(path):
     return cfg
 
 
+def load_noise_config(path):
+    """``--noise-config-yaml`` (tasks/speech_to_speech.py:82-91): noise_wav (list of WAV paths),
+    noise_prob, noise_snr ([low, high] dB), noise_num; missing keys take the reference's defaults."""
+    import yaml
+    cfg = {"noise_wav": [], "noise_prob": 0.0, "noise_snr": 0.0, "noise_num": 0}
+    with open(path) as f:
+        raw = yaml.safe_load(f) or {}
+    cfg.update({k: raw[k] for k in cfg if k in raw})
+    return cfg
+
+
 def feature_transforms(data_cfg, split, is_train):
     """fairseq ``S2TDataConfig.get_transforms``: the split's own list, else ``_train`` for a
     training split, else ``*``."""
@@ -165,11 +183,14 @@ class MultiModalS2SManifest:
     """One split of the on-disk corpus (``MultiModalSpeechToSpeechDatasetCreator._from_list``)."""
 
     def __init__(self, root, split, tgt_dict, data_cfg=None, image_feat_path=None, is_train=None,
-                 max_source_positions=6000, max_target_positions=1024, multitask=None):
-        """multitask: {task: (raw config, multitask.Dictionary)} (--multitask-config-yaml): each
+                 max_source_positions=6000, max_target_positions=1024, multitask=None, noise=None):
+        """noise: a frontend.NoiseAugment (--noise-config-yaml), mixed into every split's waveforms
+        on the GPU in front of the fbank (the reference passes one noise config to all splits).
+        multitask: {task: (raw config, multitask.Dictionary)} (--multitask-config-yaml): each
         task's text targets (``{data}/{split}.tsv``) join every collated batch as
         sample["multitask"] (speech_to_speech_dataset.py:474-521)."""
         self.root, self.split = root, split
+        self.noise = noise if noise is not None and noise.active else None
         self.multitask = {}
         if multitask:
             from . import multitask as MT
@@ -215,9 +236,12 @@ class MultiModalS2SManifest:
         return int(stem) - 1
 
     def item(self, i):
-        wav, sr = read_wav(self.audio_paths[i])
+        wav, sr, ch = read_wav_info(self.audio_paths[i])
         if sr != 16000:
             raise ValueError(f"{self.audio_paths[i]}: {sr} Hz (the fbank front end is 16 kHz)")
+        if ch > 1 and self.noise is not None:
+            # the reference mixes each channel before the mono fold; here the fold happens at read time
+            raise NotImplementedError(f"{self.audio_paths[i]}: {ch}-channel source audio with noise augmentation")
         it = {"index": i, "audio_path": self.audio_paths[i], "wave": wav,
               "n_frames": fbank_frames(len(wav)),
               "target": self.tgt_dict.encode_line(self.tgt_texts[i], append_eos=True)}
@@ -281,7 +305,8 @@ class DeviceLoader:
         self.ds, self.batches, self.cfg = dataset, list(batches), cfg
         self.device = torch.device(device)
         self.fe = frontend or fe_mod.FbankFrontend(self.device, cmvn=dataset.cmvn,
-                                                   specaugment=dataset.specaugment)
+                                                   specaugment=dataset.specaugment,
+                                                   noise=getattr(dataset, "noise", None))
         self.seed, self.epoch = seed, epoch
         self.pool = concurrent.futures.ThreadPoolExecutor(1) if prefetch else None
 
@@ -295,7 +320,7 @@ class DeviceLoader:
         if wb["order"] != list(range(len(waves))):
             raise AssertionError("front-end order differs from the collater's")
         rng = np.random.RandomState((self.seed * 1000003 + self.epoch * 7919 + b) % 2 ** 32) \
-            if self.fe.specaugment is not None else None
+            if self.fe.specaugment is not None or getattr(self.fe, "noise", None) is not None else None
         src = self.fe(wb, rng)
         return runtime.prepare_batch(sample, self.cfg, self.device, src_override=src)
 

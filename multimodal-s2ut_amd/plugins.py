@@ -216,6 +216,15 @@ class MultiModalSpeechToSpeechTask:
             for name, raw in MT.load_multitask_config(path).items():
                 dct = MT.Dictionary.load(raw["dict"])
                 self.multitask_tasks[name] = (raw, dct)
+        # speech_to_speech.py:82-91: one noise config for every split (frontend.NoiseAugment)
+        self.noise = None
+        if getattr(args, "noise_config_yaml", None):
+            from . import manifest as M
+            from .frontend import NoiseAugment
+            path = args.noise_config_yaml
+            if not os.path.isabs(path) and getattr(args, "data", None):
+                path = os.path.join(args.data, path)
+            self.noise = NoiseAugment.from_config_dict(M.load_noise_config(path))
 
     @classmethod
     def setup_task(cls, args, **kw):
@@ -253,7 +262,7 @@ class MultiModalSpeechToSpeechTask:
             image_feat_path=feat, is_train=split.startswith("train"),
             max_source_positions=getattr(a, "max_source_positions", None) or 6000,
             max_target_positions=getattr(a, "max_target_positions", None) or 1024,
-            multitask=self.multitask_tasks or None)
+            multitask=self.multitask_tasks or None, noise=self.noise)
         return self.datasets[split]
 
     def build_generator(self, models, args, **kw):
