@@ -266,6 +266,28 @@ int mms2ut_attn_softmax_bwd(const mms2ut_half* P, const mms2ut_half* dPd, mms2ut
                             int H, int Tq, int Tk, int64_t ldS, const int32_t* key_len, int causal,
                             int extra_key, float p, uint64_t seed, uint64_t offset,
                             hipStream_t stream);
+/* The same two kernels (H = 1) for the query-side fusion attention (gated fusion below), whose
+ * key / value biases travel as `npad` tail columns of the query-side matrices.  Forward: row r
+ * adds scale * q_aug[r*ld_q + 0] to the scores of keys j < n_img and scale * q_aug[r*ld_q + 1] to
+ * the keys j >= n_img before the maximum, and writes u_aug[r*ld_u + 0..npad) = {sum of Pd over
+ * j < n_img, sum over j >= n_img, 0, ...}.  Backward: du_aug[r*ld_du + 0 / 1] is added to dPd on
+ * the keys j < n_img / j >= n_img, and dq_aug[r*ld_dq + 0..npad) = {scale * sum of dS over
+ * j < n_img, scale * sum over j >= n_img, 0, ...}.  2 <= npad <= 64.                          */
+int mms2ut_attn_softmax_fwd_aug(const mms2ut_half* S, mms2ut_half* P, mms2ut_half* Pd, int Z, int Tq, int Tk,
+                                int64_t ldS, const uint8_t* key_mask, int64_t ld_mask, int extra_key, float p,
+                                uint64_t seed, uint64_t offset, const mms2ut_half* q_aug, int64_t ld_q,
+                                float scale, int n_img, mms2ut_half* u_aug, int64_t ld_u, int npad,
+                                hipStream_t stream);
+int mms2ut_attn_softmax_bwd_aug(const mms2ut_half* P, const mms2ut_half* dPd, mms2ut_half* dS, int Z, int Tq,
+                                int Tk, int64_t ldS, float p, uint64_t seed, uint64_t offset,
+                                const mms2ut_half* du_aug, int64_t ld_du, float scale, int n_img,
+                                mms2ut_half* dq_aug, int64_t ld_dq, int npad, hipStream_t stream);
+/* out[rows][Dia] = [wkv[rows][Di] | bkv | bias_kv (or 0) | 0...], and its inverse for the gradient
+ * (g_bias_kv may be NULL); rows = 2d (the K then the V half).                                  */
+int mms2ut_fusion_pack_kv(const mms2ut_half* wkv, const mms2ut_half* bkv, const mms2ut_half* bias_kv,
+                          mms2ut_half* out, int rows, int Di, int Dia, hipStream_t stream);
+int mms2ut_fusion_unpack_kv(const mms2ut_half* dw, mms2ut_half* g_wkv, mms2ut_half* g_bkv,
+                            mms2ut_half* g_bias_kv, int rows, int Di, int Dia, hipStream_t stream);
 
 /* ---------------------------------------------------------------- fused multi-head attention
  * Flash-style fwd/bwd (scores stay on chip) for fairseq MultiheadAttention in the encoder
@@ -664,7 +686,17 @@ int mms2ut_conv1d_glu_bwd(const mms2ut_conv1d_glu* c, const mms2ut_half* dy, voi
  * out = text + g (attn_out - text)) or the residual out = text + attn_out.  The output lives in
  * the arena (gated_fusion_arena's offset).  The backward writes d(text) (and with want_dimg the
  * image-feature gradient) into the scratch (offsets from gated_fusion_scratch) and the parameter
- * gradients (weight / bias gradients on `side`; g_ln / g_bias_kv are [gamma|beta], [k|v] spans).  */
+ * gradients (weight / bias gradients on `side`; g_ln / g_bias_kv are [gamma|beta], [k|v] spans).
+ *
+ * Two forms of the one-head attention compute the same function (hd = d, nothing non-linear
+ * between the k / v projections and the attention products).  The key-side form projects every
+ * image row to k|v.  The query-side form moves the projections to the B*Te query rows:
+ * S = scale (q W_k) X^T, O = (Pd X) W_v^T, with b_k, b_v and bias_kv as tail columns of
+ * [W | b | bias_kv] padded to a multiple of 64.  mms2ut_gated_fusion_route() returns the form a
+ * descriptor takes (0 key-side, 1 query-side): the one with fewer GEMM FLOPs, or the one forced by
+ * mms2ut_gated_fusion_set_route (-1 by cost, 0, 1; for tests and A/B runs; not to be changed
+ * between a forward and its backward).  Arena, scratch and workspace sizes follow the route.     */
+int mms2ut_gated_fusion_set_route(int mode);
 typedef struct mms2ut_gated_fusion {
   int B, Te, Ti, Di, d;
   int extra;                      /* multimodal_attention (add_bias_kv); 0: selective_attention  */
@@ -682,6 +714,7 @@ typedef struct mms2ut_gated_fusion {
   const mms2ut_half* img;         /* [B*Ti, Di] image features                                   */
   void* saved;
 } mms2ut_gated_fusion;
+int mms2ut_gated_fusion_route(const mms2ut_gated_fusion* f);
 int mms2ut_gated_fusion_arena(const mms2ut_gated_fusion* f, int64_t* out_offset, int64_t* bytes);
 /* offsets[0] = d(text), offsets[1] = d(img) (-1 without want_dimg)                             */
 int mms2ut_gated_fusion_scratch(const mms2ut_gated_fusion* f, int want_dimg, int64_t* offsets, int64_t* bytes);

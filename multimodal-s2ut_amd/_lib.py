@@ -178,6 +178,12 @@ SIGNATURES = {
                                       f32, u64, u64, vp]),
     "mms2ut_attn_softmax_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i64, vp, i32, i32, f32, u64,
                                       u64, vp]),
+    "mms2ut_attn_softmax_fwd_aug": (i32, [vp, vp, vp, i32, i32, i32, i64, vp, i64, i32, f32, u64, u64,
+                                          vp, i64, f32, i32, vp, i64, i32, vp]),
+    "mms2ut_attn_softmax_bwd_aug": (i32, [vp, vp, vp, i32, i32, i32, i64, f32, u64, u64, vp, i64, f32, i32,
+                                          vp, i64, i32, vp]),
+    "mms2ut_fusion_pack_kv": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mms2ut_fusion_unpack_kv": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "mms2ut_mha_varlen_fwd": (i32, [vp, vp]),   # ATTN_ARGS.pack(...) bytes
     "mms2ut_mha_varlen_bwd": (i32, [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, i64,
                                     vp, i64, i64, vp]),
@@ -217,6 +223,8 @@ SIGNATURES = {
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),
     "mms2ut_layer_fwd": (i32, [vp, vp, i64, vp]),
     "mms2ut_layer_bwd": (i32, [vp, vp, vp, vp]),
+    "mms2ut_gated_fusion_set_route": (i32, [i32]),
+    "mms2ut_gated_fusion_route": (i32, [vp]),
     "mms2ut_gated_fusion_arena": (i32, [vp, vp, vp]),
     "mms2ut_gated_fusion_scratch": (i32, [vp, i32, vp, vp]),
     "mms2ut_gated_fusion_ws": (i32, [vp, vp, vp]),

@@ -737,6 +737,17 @@ extern "C" int mms2ut_conv1d_glu_bwd(const mms2ut_conv1d_glu* c, const mms2ut_ha
 // dropout, laid out as [B][Ti (+1 bias_kv row)][Di] keys), text dropout, q / k|v projections, one-head
 // attention over the image keys (scores materialised: hd = d is past the flash kernel's head
 // sizes), out-projection, and the sigmoid gate merge (or the plain residual without the gate).
+// The attention has two forms that compute the same function (one head, nothing non-linear
+// between the k / v projections and the attention products).  Key-side: k|v = X Wkv^T + bkv over
+// all B*Tk image rows X, then S = scale q k^T, O = Pd v.  Query-side: the projections move to the
+// B*Te query rows, S = scale (q W_k) X^T and O = (Pd X) W_v^T.  There b_k, b_v and bias_kv ride as
+// tail columns: the weights are packed once per call as [W | b | bias_kv | 0] with Dia = Di + 2
+// rounded up to 64 columns, q [W_k | b_k | bias_k] carries q.b_k and q.bias_k (the softmax adds
+// them to the image keys / the bias_kv key), the softmax writes r = sum of Pd over the image keys
+// and e = Pd[:, Ti] behind U = Pd X so that [U | r | e] [W_v | b_v | bias_v]^T = O, and in the
+// backward the weight gradients dO^T [U | r | e] and q^T [dqk | ..] hold db_v, dbias_v, db_k,
+// dbias_k in the same columns (unpacked into g_wkv / g_bkv / g_bias_kv on the side stream).
+// fus_query_side() picks the form per call by GEMM FLOPs.
 // The launch sequence, arguments and stream order are model.fusion_fwd_ref / fusion_bwd_ref's, so
 // results are bit-identical to that per-launch path (tests/test_gpu_layers.py).
 namespace {
@@ -762,9 +773,33 @@ int wgrad_auto(const Ctx& c, const mms2ut_half* dy, int64_t lddy, const mms2ut_h
 }
 
 struct FusDims {
-  int64_t B, Te, Ti, Tk, Di, d, Rt, Ri, Rk, ldS;
-  bool extra, gate, pre, ln_fused;
+  int64_t B, Te, Ti, Tk, Di, Dia, d, Rt, Ri, Rk, ldS;
+  bool extra, gate, pre, ln_fused, qs;
 };
+
+// mms2ut_gated_fusion_set_route: -1 = by cost (fus_query_side), 0 = key-side, 1 = query-side
+int g_fus_route = -1;
+
+// Which form of the one-head attention costs fewer GEMM FLOPs (multiply-adds, per call; the
+// q / out / gate projections and the softmax are common to both and left out).
+//   key-side:   k|v = X Wkv^T over the Rk = B*Tk image rows, its weight gradient, and its data
+//               gradient when dX is needed: (2 + nx) * Rk * Di * 2d; six batched Te x Tk products of
+//               depth / width d (S, O, dPd, dv, dq, dk): 6 * B * Te * Tk * d.
+//   query-side: six projections over the Rt = B*Te query rows against the augmented [d, Dia]
+//               weights (q W_k, U W_v^T, dU, dW_v, dW_k, dq): 6 * Rt * Dia * d; four batched products
+//               of depth / width Di (S, U, dPd, dqk) and two more for dX = dS^T qk + Pd^T dU:
+//               (4 + 2 nx) * B * Te * Tk * Di.
+// nx = image_pre_norm: the LayerNorm's parameters need dX.  The route is fixed in the forward,
+// before want_dimg is known, so a caller-requested image gradient does not enter the count.
+// ViT features (Ti 577, Di = d = 768, Te 106): 2.3e9 B against 0.7e9 B -> query-side; DETR
+// features (Ti 100, Di 256, Te 200, d 768): 2.1e8 B against 3.3e8 B -> key-side.
+bool fus_query_side(int64_t B, int64_t Te, int64_t Tk, int64_t Di, int64_t Dia, int64_t d, bool pre) {
+  if (g_fus_route >= 0) return g_fus_route == 1;
+  const int64_t nx = pre ? 1 : 0;
+  const int64_t key = (2 + nx) * B * Tk * Di * 2 * d + 6 * B * Te * Tk * d;
+  const int64_t qry = 6 * B * Te * Dia * d + (4 + 2 * nx) * B * Te * Tk * Di;
+  return qry < key;
+}
 
 FusDims fus_dims(const mms2ut_gated_fusion* f) {
   FusDims D;
@@ -774,10 +809,13 @@ FusDims fus_dims(const mms2ut_gated_fusion* f) {
   D.Rt = D.B * D.Te; D.Ri = D.B * D.Ti; D.Rk = D.B * D.Tk;
   D.ldS = (D.Tk + 7) / 8 * 8;
   D.ln_fused = D.pre && D.Di % 256 == 0 && D.Di <= 1024;
+  D.Dia = (D.Di + 2 + 63) / 64 * 64;   // [W | b | bias_kv] padded to whole 64-wide k-tiles (LDS-DMA GEMM)
+  D.qs = fus_query_side(D.B, D.Te, D.Tk, D.Di, D.Dia, D.d, D.pre);
   return D;
 }
 
-enum { FA_IM = 0, FA_IR, FA_IMGN, FA_IMGD, FA_TEXTD, FA_Q, FA_KV, FA_S, FA_P, FA_PD, FA_O, FA_MERGE, FA_G, FA_OUT, FA_N };
+enum { FA_IM = 0, FA_IR, FA_IMGN, FA_IMGD, FA_TEXTD, FA_Q, FA_KV, FA_WAUG, FA_QK, FA_U, FA_S, FA_P, FA_PD, FA_O, FA_MERGE,
+       FA_G, FA_OUT, FA_N };
 void fus_arena_sizes(const mms2ut_gated_fusion* f, const FusDims& D, int64_t* sz) {
   for (int i = 0; i < FA_N; ++i) sz[i] = 0;
   const int64_t h = 2;
@@ -786,7 +824,12 @@ void fus_arena_sizes(const mms2ut_gated_fusion* f, const FusDims& D, int64_t* sz
   if (D.ln_fused || D.extra) sz[FA_IMGD] = D.Rk * D.Di * h;
   if (f->p_txt > 0.f) sz[FA_TEXTD] = D.Rt * D.d * h;
   sz[FA_Q] = D.Rt * D.d * h;
-  sz[FA_KV] = D.Rk * 2 * D.d * h;
+  if (D.qs) {
+    sz[FA_WAUG] = 2 * D.d * D.Dia * h;             // [W_k | b_k | bias_k], [W_v | b_v | bias_v]
+    sz[FA_QK] = sz[FA_U] = D.Rt * D.Dia * h;       // q [W_k | ..], [Pd X | r | e]
+  } else {
+    sz[FA_KV] = D.Rk * 2 * D.d * h;
+  }
   sz[FA_S] = sz[FA_P] = D.Rt * D.ldS * h;
   if (f->p_attn > 0.f) sz[FA_PD] = sz[FA_P];
   sz[FA_O] = D.Rt * D.d * h;
@@ -794,14 +837,19 @@ void fus_arena_sizes(const mms2ut_gated_fusion* f, const FusDims& D, int64_t* sz
   sz[FA_OUT] = D.Rt * D.d * h;
 }
 
-enum { FS_DPRE = 0, FS_DMERGE, FS_DO, FS_DQ, FS_DKV, FS_DPD, FS_DIMGD, FS_DIMG, FS_DIMGIN, FS_DTEXT, FS_LNP, FS_KVP,
-       FS_BPART, FS_N };
+enum { FS_DPRE = 0, FS_DMERGE, FS_DO, FS_DQ, FS_DKV, FS_DU, FS_DQK, FS_DWAUG, FS_DPD, FS_DIMGD, FS_DIMG, FS_DIMGIN, FS_DTEXT,
+       FS_LNP, FS_KVP, FS_BPART, FS_N };
 void fus_scratch_sizes(const mms2ut_gated_fusion* f, const FusDims& D, int want_dimg, int64_t* sz) {
   for (int i = 0; i < FS_N; ++i) sz[i] = 0;
   const int64_t h = 2;
   if (D.gate) { sz[FS_DPRE] = D.Rt * D.d * h; sz[FS_DMERGE] = D.Rt * 2 * D.d * h; }
   sz[FS_DO] = sz[FS_DQ] = D.Rt * D.d * h;
-  sz[FS_DKV] = D.Rk * 2 * D.d * h;
+  if (D.qs) {
+    sz[FS_DU] = sz[FS_DQK] = D.Rt * D.Dia * h;
+    sz[FS_DWAUG] = 2 * D.d * D.Dia * h;
+  } else {
+    sz[FS_DKV] = D.Rk * 2 * D.d * h;
+  }
   sz[FS_DPD] = D.Rt * D.ldS * h;
   if (D.pre || want_dimg) {
     sz[FS_DIMGD] = D.Rk * D.Di * h;
@@ -810,7 +858,7 @@ void fus_scratch_sizes(const mms2ut_gated_fusion* f, const FusDims& D, int want_
     if (D.pre) sz[FS_LNP] = (int64_t)mms2ut_layernorm_bwd_nparts(D.Ri, (int)D.Di) * 2 * D.Di * 4;
   }
   sz[FS_DTEXT] = D.Rt * D.d * h;
-  if (D.extra) sz[FS_KVP] = (int64_t)mms2ut_colsum_nparts(D.B) * 2 * D.d * 4;
+  if (D.extra && !D.qs) sz[FS_KVP] = (int64_t)mms2ut_colsum_nparts(D.B) * 2 * D.d * 4;
   sz[FS_BPART] = (int64_t)mms2ut_colsum_nparts(std::max(D.Rt, D.Rk)) * 2 * D.d * 4;
 }
 
@@ -845,6 +893,17 @@ int zero_rows(mms2ut_half* p, int64_t pitch_elems, int64_t width_elems, int64_t 
 }
 
 }  // namespace
+
+extern "C" int mms2ut_gated_fusion_set_route(int mode) {
+  MMS_REQUIRE(mode >= -1 && mode <= 1, "gated_fusion_set_route: mode must be -1, 0 or 1 (got %d)", mode);
+  g_fus_route = mode;
+  return 0;
+}
+
+extern "C" int mms2ut_gated_fusion_route(const mms2ut_gated_fusion* f) {
+  if (fus_check(f)) return -1;
+  return fus_dims(f).qs ? 1 : 0;
+}
 
 extern "C" int mms2ut_gated_fusion_arena(const mms2ut_gated_fusion* f, int64_t* out_offset, int64_t* bytes) {
   if (int rc = fus_check(f)) return rc;
@@ -886,9 +945,16 @@ extern "C" int mms2ut_gated_fusion_ws(const mms2ut_gated_fusion* f, int64_t* mai
     sw = std::max(sw, (int64_t)s * N * K + (int64_t)s * N);
   };
   const int64_t d = D.d;
-  fw(D.Rt, d, d); fw(D.Rk, 2 * d, D.Di); fw(D.Rt, d, d); fw(D.Rt, d, 2 * d);      // forward
-  fw(D.Rt, 2 * d, d); fw(D.Rt, d, d); fw(D.Rk, D.Di, 2 * d); fw(D.Rt, d, d);      // dgrads
-  ww(D.Rt, d, 2 * d); ww(D.Rt, d, d); ww(D.Rk, 2 * d, D.Di); ww(D.Rt, d, d);      // weight gradients
+  fw(D.Rt, d, d); fw(D.Rt, d, d); fw(D.Rt, d, 2 * d);                             // forward
+  fw(D.Rt, 2 * d, d); fw(D.Rt, d, d); fw(D.Rt, d, d);                             // dgrads
+  ww(D.Rt, d, 2 * d); ww(D.Rt, d, d); ww(D.Rt, d, d);                             // weight gradients
+  if (D.qs) {
+    fw(D.Rt, D.Dia, d); fw(D.Rt, d, D.Dia);                                       // q W_k / dU, U W_v^T / dq
+    ww(D.Rt, d, D.Dia);                                                           // dW_v, dW_k
+  } else {
+    fw(D.Rk, 2 * d, D.Di); fw(D.Rk, D.Di, 2 * d);
+    ww(D.Rk, 2 * d, D.Di);
+  }
   *main_floats = mw;
   *side_floats = sw;
   return 0;
@@ -943,22 +1009,41 @@ extern "C" int mms2ut_gated_fusion_fwd(const mms2ut_gated_fusion* f, float* main
   }
   mms2ut_half *q = H_(FA_Q), *kv = H_(FA_KV), *O = H_(FA_O);
   if ((rc = linear(c, textd, f->wq, f->bq, q, D.Rt, d, d))) return rc;
-  if ((rc = linear(c, imgd, f->wkv, f->bkv, kv, D.Rk, 2 * d, Di))) return rc;
-  if (D.extra && (rc = mms2ut_copy2d(f->bias_kv, 0, kv + D.Ti * 2 * d, D.Tk * 2 * d, D.B, (int)(2 * d), s))) return rc;
-  // one-head attention, scores materialised (model.attn_fwd)
   const float scale = (float)pow((double)d, -0.5);
   mms2ut_half *S = H_(FA_S), *P = H_(FA_P), *Pd = f->p_attn > 0.f ? H_(FA_PD) : P;
-  {
+  if (D.qs) {
+    // query-side form: S = scale (q W_k) X^T, O = (Pd X) W_v^T; b_k, b_v and bias_kv ride in the
+    // tail columns of the augmented weights / qk / U (the softmax adds and writes them)
+    const int64_t Dia = D.Dia;
+    mms2ut_half *waug = H_(FA_WAUG), *qk = H_(FA_QK), *U = H_(FA_U);
+    if ((rc = mms2ut_fusion_pack_kv(f->wkv, f->bkv, D.extra ? f->bias_kv : nullptr, waug, (int)(2 * d), (int)Di,
+                                    (int)Dia, s))) return rc;
+    if ((rc = gemm_nt(c, q, d, waug, Dia, 0, qk, Dia, D.Rt, Dia, d, MMS_EPI_F16, nullptr, nullptr, 0, 0.f, 0, 0, Dia)))
+      return rc;
+    mms2ut_gemm_args a = batched(qk, imgd, S, (int)D.Te, (int)D.Tk, (int)Di, 1, 1, Dia, Di, D.ldS, (int)D.B, D.Te * Dia,
+                                 D.Tk * Di, D.Te * D.ldS, scale);
+    if ((rc = mms2ut_gemm_f16(&a, s))) return rc;
+    if ((rc = mms2ut_attn_softmax_fwd_aug(S, P, Pd, (int)D.B, (int)D.Te, (int)D.Tk, D.ldS, f->key_mask,
+                                          f->key_mask ? f->ld_mask : 0, D.extra ? 1 : 0, f->p_attn,
+                                          f->p_attn > 0.f ? f->seed : 0, f->p_attn > 0.f ? f->off_attn : 0, qk + Di, Dia,
+                                          scale, (int)D.Ti, U + Di, Dia, (int)(Dia - Di), s))) return rc;
+    a = batched(Pd, imgd, U, (int)D.Te, (int)Di, (int)D.Tk, 1, 0, D.ldS, Di, Dia, (int)D.B, D.Te * D.ldS, D.Tk * Di,
+                D.Te * Dia, 1.f);
+    if ((rc = mms2ut_gemm_f16(&a, s))) return rc;
+    if ((rc = gemm_nt(c, U, Dia, waug + d * Dia, Dia, 1, O, d, D.Rt, d, Dia, MMS_EPI_F16, nullptr, nullptr, 0, 0.f, 0, 0,
+                      d))) return rc;
+  } else {
+    if ((rc = linear(c, imgd, f->wkv, f->bkv, kv, D.Rk, 2 * d, Di))) return rc;
+    if (D.extra && (rc = mms2ut_copy2d(f->bias_kv, 0, kv + D.Ti * 2 * d, D.Tk * 2 * d, D.B, (int)(2 * d), s))) return rc;
+    // one-head attention, scores materialised (model.attn_fwd)
     mms2ut_gemm_args a = batched(q, kv, S, (int)D.Te, (int)D.Tk, (int)d, 1, 1, d, 2 * d, D.ldS, (int)D.B, D.Te * d,
                                  D.Tk * 2 * d, D.Te * D.ldS, scale);
     if ((rc = mms2ut_gemm_f16(&a, s))) return rc;
-  }
-  if ((rc = mms2ut_attn_softmax_fwd(S, P, Pd, (int)D.B, 1, (int)D.Te, (int)D.Tk, D.ldS, nullptr, f->key_mask,
-                                    f->key_mask ? f->ld_mask : 0, 0, D.extra ? 1 : 0, f->p_attn,
-                                    f->p_attn > 0.f ? f->seed : 0, f->p_attn > 0.f ? f->off_attn : 0, s))) return rc;
-  {
-    mms2ut_gemm_args a = batched(Pd, kv + d, O, (int)D.Te, (int)d, (int)D.Tk, 1, 0, D.ldS, 2 * d, d, (int)D.B,
-                                 D.Te * D.ldS, D.Tk * 2 * d, D.Te * d, 1.f);
+    if ((rc = mms2ut_attn_softmax_fwd(S, P, Pd, (int)D.B, 1, (int)D.Te, (int)D.Tk, D.ldS, nullptr, f->key_mask,
+                                      f->key_mask ? f->ld_mask : 0, 0, D.extra ? 1 : 0, f->p_attn,
+                                      f->p_attn > 0.f ? f->seed : 0, f->p_attn > 0.f ? f->off_attn : 0, s))) return rc;
+    a = batched(Pd, kv + d, O, (int)D.Te, (int)d, (int)D.Tk, 1, 0, D.ldS, 2 * d, d, (int)D.B, D.Te * D.ldS, D.Tk * 2 * d,
+                D.Te * d, 1.f);
     if ((rc = mms2ut_gemm_f16(&a, s))) return rc;
   }
   mms2ut_half* out = H_(FA_OUT);
@@ -1025,33 +1110,62 @@ extern "C" int mms2ut_gated_fusion_bwd(const mms2ut_gated_fusion* f, const mms2u
   mms2ut_half *dq = SH(FS_DQ), *dkv = SH(FS_DKV), *dPd = SH(FS_DPD);
   const int B = (int)D.B, Te = (int)D.Te, Tk = (int)D.Tk;
   const int64_t sS = D.Te * D.ldS;
-  {
+  if (D.qs) {
+    const int64_t Dia = D.Dia;
+    const mms2ut_half *waug = H_(FA_WAUG), *qk = H_(FA_QK), *U = H_(FA_U);
+    mms2ut_half *dU = SH(FS_DU), *dqk = SH(FS_DQK), *dwa = SH(FS_DWAUG);
+    // dU | dO.b_v | dO.bias_v = dO [W_v | b_v | bias_v];  dW_v | db_v | dbias_v = dO^T [U | r | e]
+    if ((rc = gemm_nt(c, dO, d, waug + d * Dia, Dia, 0, dU, Dia, D.Rt, Dia, d, MMS_EPI_F16, nullptr, nullptr, 0, 0.f, 0, 0,
+                      Dia))) return rc;
+    if ((rc = wgrad_auto(c, dO, d, U, Dia, dwa + d * Dia, nullptr, D.Rt, d, Dia, side_blocks))) return rc;
+    mms2ut_gemm_args a = batched(dU, imgd, dPd, Te, Tk, (int)Di, 1, 1, Dia, Di, D.ldS, B, D.Te * Dia, D.Tk * Di, sS, 1.f);
+    if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
+    if ((rc = mms2ut_attn_softmax_bwd_aug(P, dPd, dPd, B, Te, Tk, D.ldS, f->p_attn, f->p_attn > 0.f ? f->seed : 0,
+                                          f->p_attn > 0.f ? f->off_attn : 0, dU + Di, Dia, scale, (int)D.Ti, dqk + Di,
+                                          Dia, (int)(Dia - Di), main))) return rc;
+    // dqk = scale dS X (tail columns from the softmax);  dW_k | db_k | dbias_k = q^T dqk
+    a = batched(dPd, imgd, dqk, Te, (int)Di, Tk, 1, 0, D.ldS, Di, Dia, B, sS, D.Tk * Di, D.Te * Dia, scale);
+    if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
+    if ((rc = wgrad_auto(c, q, d, dqk, Dia, dwa, nullptr, D.Rt, d, Dia, side_blocks))) return rc;
+    if ((rc = fork(c)) ||
+        (rc = mms2ut_fusion_unpack_kv(dwa, f->g_wkv, f->g_bkv, D.extra ? f->g_bias_kv : nullptr, (int)(2 * d), (int)Di,
+                                      (int)Dia, side))) return rc;
+    if ((rc = gemm_nt(c, dqk, Dia, waug, Dia, 1, dq, d, D.Rt, d, Dia, MMS_EPI_F16, nullptr, nullptr, 0, 0.f, 0, 0, d)))
+      return rc;
+    if (D.pre || want_dimg) {
+      // dX = scale dS^T qk + Pd^T dU (the bias_kv row of X is a constant: its gradient row is unused)
+      mms2ut_half* dimgd = SH(FS_DIMGD);
+      a = batched(dPd, qk, dimgd, Tk, (int)Di, Te, 0, 0, D.ldS, Dia, Di, B, sS, D.Te * Dia, D.Tk * Di, scale);
+      if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
+      a = batched(Pd, dU, dimgd, Tk, (int)Di, Te, 0, 0, D.ldS, Dia, Di, B, sS, D.Te * Dia, D.Tk * Di, 1.f);
+      a.epi = MMS_EPI_F16_ACC;
+      if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
+    }
+  } else {
     mms2ut_gemm_args a = batched(dO, kv + d, dPd, Te, Tk, (int)d, 1, 1, d, 2 * d, D.ldS, B, D.Te * d, D.Tk * 2 * d, sS, 1.f);
     if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
     a = batched(Pd, dO, dkv + d, Tk, (int)d, Te, 0, 0, D.ldS, d, 2 * d, B, sS, D.Te * d, D.Tk * 2 * d, 1.f);
     if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
-  }
-  if ((rc = mms2ut_attn_softmax_bwd(P, dPd, dPd, B, 1, Te, Tk, D.ldS, nullptr, 0, 0, f->p_attn,
-                                    f->p_attn > 0.f ? f->seed : 0, f->p_attn > 0.f ? f->off_attn : 0, main))) return rc;
-  {
-    mms2ut_gemm_args a = batched(dPd, kv, dq, Te, (int)d, Tk, 1, 0, D.ldS, 2 * d, d, B, sS, D.Tk * 2 * d, D.Te * d, scale);
+    if ((rc = mms2ut_attn_softmax_bwd(P, dPd, dPd, B, 1, Te, Tk, D.ldS, nullptr, 0, 0, f->p_attn,
+                                      f->p_attn > 0.f ? f->seed : 0, f->p_attn > 0.f ? f->off_attn : 0, main))) return rc;
+    a = batched(dPd, kv, dq, Te, (int)d, Tk, 1, 0, D.ldS, 2 * d, d, B, sS, D.Tk * 2 * d, D.Te * d, scale);
     if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
     a = batched(dPd, q, dkv, Tk, (int)d, Te, 0, 0, D.ldS, d, 2 * d, B, sS, D.Te * d, D.Tk * 2 * d, scale);
     if ((rc = mms2ut_gemm_f16(&a, main))) return rc;
+    if (D.extra) {
+      // bias_k / bias_v gradients: the batch sum of the extra key row's gradient (main stream), then
+      // that row is zeroed for the k|v weight gradient
+      mms2ut_half* rows = dkv + D.Ti * 2 * d;
+      const int np = mms2ut_colsum_nparts(D.B);
+      if ((rc = mms2ut_colsum_f16(rows, D.B, (int)(2 * d), D.Tk * 2 * d, SF(FS_KVP), np, main))) return rc;
+      if ((rc = mms2ut_colsum_parts(SF(FS_KVP), np, (int)(2 * d), f->g_bias_kv, 0, main))) return rc;
+      if ((rc = zero_rows(rows, D.Tk * 2 * d, 2 * d, D.B, main))) return rc;
+    }
+    if ((rc = wgrad_auto(c, dkv, 2 * d, imgd, Di, f->g_wkv, f->g_bkv, D.Rk, 2 * d, Di, side_blocks))) return rc;
   }
-  if (D.extra) {
-    // bias_k / bias_v gradients: the batch sum of the extra key row's gradient (main stream), then
-    // that row is zeroed for the k|v weight gradient
-    mms2ut_half* rows = dkv + D.Ti * 2 * d;
-    const int np = mms2ut_colsum_nparts(D.B);
-    if ((rc = mms2ut_colsum_f16(rows, D.B, (int)(2 * d), D.Tk * 2 * d, SF(FS_KVP), np, main))) return rc;
-    if ((rc = mms2ut_colsum_parts(SF(FS_KVP), np, (int)(2 * d), f->g_bias_kv, 0, main))) return rc;
-    if ((rc = zero_rows(rows, D.Tk * 2 * d, 2 * d, D.B, main))) return rc;
-  }
-  if ((rc = wgrad_auto(c, dkv, 2 * d, imgd, Di, f->g_wkv, f->g_bkv, D.Rk, 2 * d, Di, side_blocks))) return rc;
   if (D.ln_fused) {
     mms2ut_half* dimgd = SH(FS_DIMGD);
-    if ((rc = dgrad(c, dkv, 2 * d, f->wkv, f->wt_kv, dimgd, D.Rk, 2 * d, Di))) return rc;
+    if (!D.qs && (rc = dgrad(c, dkv, 2 * d, f->wkv, f->wt_kv, dimgd, D.Rk, 2 * d, Di))) return rc;
     if ((rc = mms2ut_layernorm_bwd_ex(dimgd, f->img, f->ln_g, at<float>(A, off, FA_IM), at<float>(A, off, FA_IR), nullptr,
                                       want_dimg ? SH(FS_DIMGIN) : nullptr, SF(FS_LNP), D.Ri, (int)Di, nullptr, 0.f, 0, 0,
                                       D.extra ? D.Ti : 0, D.extra ? D.Tk : 0, f->p_img, f->p_img > 0.f ? f->seed : 0,
@@ -1061,7 +1175,7 @@ extern "C" int mms2ut_gated_fusion_bwd(const mms2ut_gated_fusion* f, const mms2u
       return rc;
   } else if (D.pre || want_dimg) {
     mms2ut_half* dimgd = SH(FS_DIMGD);
-    if ((rc = dgrad(c, dkv, 2 * d, f->wkv, f->wt_kv, dimgd, D.Rk, 2 * d, Di))) return rc;
+    if (!D.qs && (rc = dgrad(c, dkv, 2 * d, f->wkv, f->wt_kv, dimgd, D.Rk, 2 * d, Di))) return rc;
     mms2ut_half* dimg = dimgd;
     if (D.extra) {
       dimg = SH(FS_DIMG);

@@ -478,6 +478,18 @@ __global__ void __launch_bounds__(256) colsum_f16_kernel(const h16* __restrict__
 
 // ============================================================================ attention softmax
 // One wave per score row; lane owns contiguous 4-key chunks (chunk = lane + 64*c).
+// Query-side fusion attention (csrc/layers.hip): `in` = two per-row terms (image keys j < n_img,
+// then the bias_kv key), `out` = npad per-row tail columns the kernel writes ({sum over the image
+// keys, the bias_kv key's value, 0...}); both null for the plain softmax.
+struct SoftmaxAug {
+  const h16* in;
+  long ld_in;
+  h16* out;
+  long ld_out;
+  int n_img, npad;
+  float scale;
+};
+
 MMS_DEV bool key_valid(int j, int i, int Tk, int klen, const uint8_t* km, int causal, int extra_key) {
   if (j >= Tk) return false;
   if (extra_key && j == Tk - 1) return true;
@@ -493,12 +505,18 @@ __global__ void __launch_bounds__(256) softmax_fwd_kernel(const h16* __restrict_
                                                           long ldS, const int* __restrict__ key_len,
                                                           const uint8_t* __restrict__ key_mask, long ld_mask,
                                                           int causal, int extra_key, float p, uint32_t thresh,
-                                                          uint64_t seed, uint64_t offset) {
+                                                          uint64_t seed, uint64_t offset, SoftmaxAug aug) {
   if (thresh) seed = mms_step_seed(seed);
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long)Z * Tq) return;
   const int z = (int)(row / Tq), i = (int)(row % Tq);
+  // query-side fusion attention: per-row score terms of the image keys / the bias_kv key
+  float add0 = 0.f, add1 = 0.f;
+  if (aug.in) {
+    add0 = aug.scale * (float)aug.in[row * aug.ld_in];
+    add1 = aug.scale * (float)aug.in[row * aug.ld_in + 1];
+  }
   const int b = z / H;
   const int klen = key_len ? key_len[b] : Tk;
   const uint8_t* km = key_mask ? key_mask + (long)b * ld_mask : nullptr;
@@ -513,7 +531,8 @@ __global__ void __launch_bounds__(256) softmax_fwd_kernel(const h16* __restrict_
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int j = j0 + e;
-        v[c][e] = key_valid(j, i, Tk, klen, km, causal, extra_key) ? (float)t[e] : -INFINITY;
+        v[c][e] = key_valid(j, i, Tk, klen, km, causal, extra_key)
+                      ? (float)t[e] + (aug.in ? (j < aug.n_img ? add0 : add1) : 0.f) : -INFINITY;
         mx = fmaxf(mx, v[c][e]);
       }
     } else {
@@ -536,6 +555,7 @@ __global__ void __launch_bounds__(256) softmax_fwd_kernel(const h16* __restrict_
   const float ds = thresh ? 1.f / (1.f - p) : 1.f;
   h16* pr = P + row * ldS;
   h16* pdr = Pd + row * ldS;
+  float r_img = 0.f, r_ext = 0.f;   // sums of Pd over the image keys / at the bias_kv key
 #pragma unroll
   for (int c = 0; c < CPL; ++c) {
     const int j0 = (lane + c * 64) * 4;
@@ -549,10 +569,18 @@ __global__ void __launch_bounds__(256) softmax_fwd_kernel(const h16* __restrict_
           const bool keep = mms_keep(seed, offset + (uint64_t)row * Tk + (j0 + e), thresh);
           od[e] = keep ? o[e] * ds : 0.f;
         }
+        if (aug.out) {
+          if (j0 + e < aug.n_img) r_img += od[e]; else r_ext += od[e];
+        }
       }
       st4(pr + j0, o[0], o[1], o[2], o[3]);
       if (thresh) st4(pdr + j0, od[0], od[1], od[2], od[3]);
     }
+  }
+  if (aug.out) {
+    r_img = wave_sum(r_img);
+    r_ext = wave_sum(r_ext);
+    if (lane < aug.npad) aug.out[row * aug.ld_out + lane] = (h16)(lane == 0 ? r_img : lane == 1 ? r_ext : 0.f);
   }
 }
 
@@ -560,12 +588,18 @@ template <int CPL>
 __global__ void __launch_bounds__(256) softmax_bwd_kernel(const h16* __restrict__ P, const h16* __restrict__ dPd,
                                                           h16* __restrict__ dS, int Z, int H, int Tq, int Tk,
                                                           long ldS, float p, uint32_t thresh, uint64_t seed,
-                                                          uint64_t offset) {
+                                                          uint64_t offset, SoftmaxAug aug) {
   if (thresh) seed = mms_step_seed(seed);
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long)Z * Tq) return;
   const float ds = thresh ? 1.f / (1.f - p) : 1.f;
+  // query-side fusion attention: d(Pd) terms of the image keys / the bias_kv key (dO.b_v, dO.bias_v)
+  float add0 = 0.f, add1 = 0.f;
+  if (aug.in) {
+    add0 = (float)aug.in[row * aug.ld_in];
+    add1 = (float)aug.in[row * aug.ld_in + 1];
+  }
   float pv[CPL][4], gv[CPL][4];
   float s = 0.f;
 #pragma unroll
@@ -579,7 +613,7 @@ __global__ void __launch_bounds__(256) softmax_bwd_kernel(const h16* __restrict_
         float m = ds;
         if (thresh && j < Tk) m = mms_keep(seed, offset + (uint64_t)row * Tk + j, thresh) ? ds : 0.f;
         pv[c][e] = (j < Tk) ? (float)a[e] : 0.f;
-        gv[c][e] = (j < Tk) ? (float)g[e] * m : 0.f;  // dP (undropped grad)
+        gv[c][e] = (j < Tk) ? ((float)g[e] + (aug.in ? (j < aug.n_img ? add0 : add1) : 0.f)) * m : 0.f;  // dP (undropped grad)
         s += pv[c][e] * gv[c][e];
       }
     } else {
@@ -588,17 +622,58 @@ __global__ void __launch_bounds__(256) softmax_bwd_kernel(const h16* __restrict_
     }
   }
   s = wave_sum(s);
+  float t_img = 0.f, t_ext = 0.f;   // sums of dS over the image keys / at the bias_kv key
 #pragma unroll
   for (int c = 0; c < CPL; ++c) {
     const int j0 = (lane + c * 64) * 4;
     if (j0 < Tk) {
       float o[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = pv[c][e] * (gv[c][e] - s);
+      for (int e = 0; e < 4; ++e) {
+        o[e] = pv[c][e] * (gv[c][e] - s);
+        if (aug.out) {
+          if (j0 + e < aug.n_img) t_img += o[e]; else t_ext += o[e];
+        }
+      }
       st4(dS + row * ldS + j0, o[0], o[1], o[2], o[3]);
     }
   }
+  if (aug.out) {
+    t_img = wave_sum(t_img);
+    t_ext = wave_sum(t_ext);
+    if (lane < aug.npad)
+      aug.out[row * aug.ld_out + lane] = (h16)(lane == 0 ? aug.scale * t_img : lane == 1 ? aug.scale * t_ext : 0.f);
+  }
   (void)Z; (void)H;
+}
+
+// ============================================================================ fusion k|v augmentation
+// out[2d][Dia] = [W_kv | b_kv | bias_kv | 0]: the query-side fusion attention's projection operand
+__global__ void fusion_pack_kv_kernel(const h16* __restrict__ wkv, const h16* __restrict__ bkv,
+                                      const h16* __restrict__ bias_kv, h16* __restrict__ out, int rows, int Di,
+                                      int Dia) {
+  const long n = (long)rows * Dia;
+  for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
+    const int r = (int)(t / Dia), i = (int)(t % Dia);
+    h16 v = (h16)0.f;
+    if (i < Di) v = wkv[(long)r * Di + i];
+    else if (i == Di) v = bkv[r];
+    else if (i == Di + 1 && bias_kv) v = bias_kv[r];
+    out[t] = v;
+  }
+}
+
+// the augmented weight gradient dw[2d][Dia] -> g_wkv [2d][Di], g_bkv [2d], g_bias_kv [2d] (or null)
+__global__ void fusion_unpack_kv_kernel(const h16* __restrict__ dw, h16* __restrict__ g_wkv, h16* __restrict__ g_bkv,
+                                        h16* __restrict__ g_bias_kv, int rows, int Di, int Dia) {
+  const long n = (long)rows * Dia;
+  for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
+    const int r = (int)(t / Dia), i = (int)(t % Dia);
+    const h16 v = dw[t];
+    if (i < Di) g_wkv[(long)r * Di + i] = v;
+    else if (i == Di) g_bkv[r] = v;
+    else if (i == Di + 1 && g_bias_kv) g_bias_kv[r] = v;
+  }
 }
 
 // ============================================================================ elementwise
@@ -1098,10 +1173,10 @@ extern "C" int mms2ut_colsum_f16(const h16* x, int64_t rows, int cols, int64_t l
   return mms::check_launch("colsum_f16");
 }
 
-extern "C" int mms2ut_attn_softmax_fwd(const h16* S, h16* P, h16* Pd, int Z, int H, int Tq, int Tk,
-                                       int64_t ldS, const int32_t* key_len, const uint8_t* key_mask,
-                                       int64_t ld_mask, int causal, int extra_key,
-                                       float p, uint64_t seed, uint64_t offset, hipStream_t s) {
+static int softmax_fwd_launch(const h16* S, h16* P, h16* Pd, int Z, int H, int Tq, int Tk, int64_t ldS,
+                              const int32_t* key_len, const uint8_t* key_mask, int64_t ld_mask, int causal,
+                              int extra_key, float p, uint64_t seed, uint64_t offset, const SoftmaxAug& aug,
+                              hipStream_t s) {
   MMS_REQUIRE(ldS % 4 == 0 && ldS >= Tk, "softmax: ldS must be a multiple of 4 and >= Tk");
   MMS_REQUIRE(p < 1.f, "softmax: p must be < 1");
   const long rows = (long)Z * Tq;
@@ -1110,8 +1185,44 @@ extern "C" int mms2ut_attn_softmax_fwd(const h16* S, h16* P, h16* Pd, int Z, int
   return pick_cpl((Tk + 3) / 4, [&](auto C) {
     hipLaunchKernelGGL((softmax_fwd_kernel<decltype(C)::value>), dim3((rows + 3) / 4), dim3(256), 0, s,
                        S, P, Pd, Z, H, Tq, Tk, (long)ldS, key_len, key_mask, (long)ld_mask, causal,
-                       extra_key, p, th, seed, offset);
+                       extra_key, p, th, seed, offset, aug);
     return mms::check_launch("attn_softmax_fwd");
+  });
+}
+
+extern "C" int mms2ut_attn_softmax_fwd(const h16* S, h16* P, h16* Pd, int Z, int H, int Tq, int Tk,
+                                       int64_t ldS, const int32_t* key_len, const uint8_t* key_mask,
+                                       int64_t ld_mask, int causal, int extra_key,
+                                       float p, uint64_t seed, uint64_t offset, hipStream_t s) {
+  return softmax_fwd_launch(S, P, Pd, Z, H, Tq, Tk, ldS, key_len, key_mask, ld_mask, causal, extra_key, p, seed,
+                            offset, SoftmaxAug{}, s);
+}
+
+static bool aug_ok(const h16* in, int64_t ld_in, const h16* out, int64_t ld_out, int n_img, int npad, int Tk) {
+  return in && out && ld_in >= 2 && ld_out >= npad && npad >= 2 && npad <= 64 && n_img >= 0 && n_img <= Tk;
+}
+
+extern "C" int mms2ut_attn_softmax_fwd_aug(const h16* S, h16* P, h16* Pd, int Z, int Tq, int Tk, int64_t ldS,
+                                           const uint8_t* key_mask, int64_t ld_mask, int extra_key, float p,
+                                           uint64_t seed, uint64_t offset, const h16* q_aug, int64_t ld_q,
+                                           float scale, int n_img, h16* u_aug, int64_t ld_u, int npad,
+                                           hipStream_t s) {
+  MMS_REQUIRE(aug_ok(q_aug, ld_q, u_aug, ld_u, n_img, npad, Tk), "softmax_fwd_aug: bad augmentation columns");
+  const SoftmaxAug aug{q_aug, (long)ld_q, u_aug, (long)ld_u, n_img, npad, scale};
+  return softmax_fwd_launch(S, P, Pd, Z, 1, Tq, Tk, ldS, nullptr, key_mask, ld_mask, 0, extra_key, p, seed, offset,
+                            aug, s);
+}
+
+static int softmax_bwd_launch(const h16* P, const h16* dPd, h16* dS, int Z, int H, int Tq, int Tk, int64_t ldS,
+                              float p, uint64_t seed, uint64_t offset, const SoftmaxAug& aug, hipStream_t s) {
+  MMS_REQUIRE(ldS % 4 == 0 && ldS >= Tk, "softmax_bwd: ldS must be a multiple of 4 and >= Tk");
+  const long rows = (long)Z * Tq;
+  if (rows == 0) return 0;
+  const uint32_t th = mms_drop_thresh(p);
+  return pick_cpl((Tk + 3) / 4, [&](auto C) {
+    hipLaunchKernelGGL((softmax_bwd_kernel<decltype(C)::value>), dim3((rows + 3) / 4), dim3(256), 0, s,
+                       P, dPd, dS, Z, H, Tq, Tk, (long)ldS, p, th, seed, offset, aug);
+    return mms::check_launch("attn_softmax_bwd");
   });
 }
 
@@ -1119,16 +1230,37 @@ extern "C" int mms2ut_attn_softmax_bwd(const h16* P, const h16* dPd, h16* dS, in
                                        int Tk, int64_t ldS, const int32_t* key_len, int causal,
                                        int extra_key, float p, uint64_t seed, uint64_t offset,
                                        hipStream_t s) {
-  MMS_REQUIRE(ldS % 4 == 0 && ldS >= Tk, "softmax_bwd: ldS must be a multiple of 4 and >= Tk");
-  const long rows = (long)Z * Tq;
-  if (rows == 0) return 0;
-  const uint32_t th = mms_drop_thresh(p);
   (void)key_len; (void)causal; (void)extra_key;  // masked entries have P == 0 -> dS == 0
-  return pick_cpl((Tk + 3) / 4, [&](auto C) {
-    hipLaunchKernelGGL((softmax_bwd_kernel<decltype(C)::value>), dim3((rows + 3) / 4), dim3(256), 0, s,
-                       P, dPd, dS, Z, H, Tq, Tk, (long)ldS, p, th, seed, offset);
-    return mms::check_launch("attn_softmax_bwd");
-  });
+  return softmax_bwd_launch(P, dPd, dS, Z, H, Tq, Tk, ldS, p, seed, offset, SoftmaxAug{}, s);
+}
+
+extern "C" int mms2ut_attn_softmax_bwd_aug(const h16* P, const h16* dPd, h16* dS, int Z, int Tq, int Tk,
+                                           int64_t ldS, float p, uint64_t seed, uint64_t offset, const h16* du_aug,
+                                           int64_t ld_du, float scale, int n_img, h16* dq_aug, int64_t ld_dq,
+                                           int npad, hipStream_t s) {
+  MMS_REQUIRE(aug_ok(du_aug, ld_du, dq_aug, ld_dq, n_img, npad, Tk), "softmax_bwd_aug: bad augmentation columns");
+  const SoftmaxAug aug{du_aug, (long)ld_du, dq_aug, (long)ld_dq, n_img, npad, scale};
+  return softmax_bwd_launch(P, dPd, dS, Z, 1, Tq, Tk, ldS, p, seed, offset, aug, s);
+}
+
+extern "C" int mms2ut_fusion_pack_kv(const h16* wkv, const h16* bkv, const h16* bias_kv, h16* out, int rows,
+                                     int Di, int Dia, hipStream_t s) {
+  MMS_REQUIRE(wkv && bkv && out && rows > 0 && Di > 0 && Dia >= Di + 2, "fusion_pack_kv: bad arguments");
+  const long n = (long)rows * Dia;
+  const long nb = (n + 255) / 256;
+  hipLaunchKernelGGL(fusion_pack_kv_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s,
+                     wkv, bkv, bias_kv, out, rows, Di, Dia);
+  return mms::check_launch("fusion_pack_kv");
+}
+
+extern "C" int mms2ut_fusion_unpack_kv(const h16* dw, h16* g_wkv, h16* g_bkv, h16* g_bias_kv, int rows, int Di,
+                                       int Dia, hipStream_t s) {
+  MMS_REQUIRE(dw && g_wkv && g_bkv && rows > 0 && Di > 0 && Dia >= Di + 2, "fusion_unpack_kv: bad arguments");
+  const long n = (long)rows * Dia;
+  const long nb = (n + 255) / 256;
+  hipLaunchKernelGGL(fusion_unpack_kv_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s,
+                     dw, g_wkv, g_bkv, g_bias_kv, rows, Di, Dia);
+  return mms::check_launch("fusion_unpack_kv");
 }
 
 extern "C" int mms2ut_dropout_fwd(const h16* x, h16* y, int64_t n, float p, uint64_t seed,

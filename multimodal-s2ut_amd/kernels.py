@@ -463,6 +463,40 @@ class ConvCall:
             _Side.used = True
 
 
+def fusion_route(a):
+    """Which form of the fusion attention the library takes for the argument block `a`
+    (_lib.FusionArgs): 0 key-side, 1 query-side (include/mms2ut.h mms2ut_gated_fusion_route)."""
+    r = _lib.load().mms2ut_gated_fusion_route(ctypes.byref(a))
+    if r < 0:
+        raise RuntimeError("mms2ut_gated_fusion_route: " + _lib.load().mms2ut_last_error().decode())
+    return r
+
+
+def fusion_set_route(mode):
+    """Force a form of the fusion attention (tests, A/B runs): -1 by cost, 0 key-side, 1 query-side.
+    Not to be changed between a forward and its backward."""
+    call("mms2ut_gated_fusion_set_route", int(mode))
+
+
+def fusion_pack_kv(Wkv, bkv, bias_kv, Dia):
+    """[2d, Dia] = [Wkv | bkv | bias_kv (or 0) | 0...] (mms2ut_fusion_pack_kv)."""
+    rows, Di = Wkv.shape
+    assert Wkv.is_contiguous() and bkv.is_contiguous() and (bias_kv is None or bias_kv.is_contiguous())
+    out = torch.empty(rows, Dia, dtype=F16, device=Wkv.device)
+    call("mms2ut_fusion_pack_kv", Wkv.data_ptr(), bkv.data_ptr(), _p(bias_kv), out.data_ptr(), rows, Di, Dia, _s())
+    return out
+
+
+def fusion_unpack_kv(dw, gWkv, gbkv, g_bias_kv):
+    """The inverse of fusion_pack_kv for the augmented weight gradient, on the side stream."""
+    rows, Di = gWkv.shape
+    assert gWkv.is_contiguous() and gbkv.is_contiguous() and dw.is_contiguous()
+    ctx = side_begin(dw)
+    with (ctx or _NULLCTX):
+        call("mms2ut_fusion_unpack_kv", dw.data_ptr(), gWkv.data_ptr(), gbkv.data_ptr(), _p(g_bias_kv), rows, Di,
+             dw.shape[1], _s())
+
+
 class FusionCall:
     """The fusion tail (image LN, q / k|v projections, one-head attention, out-projection, sigmoid
     gate) enqueued by one library call each way (include/mms2ut.h mms2ut_gated_fusion_fwd / _bwd).
@@ -492,11 +526,17 @@ class FusionCall:
             setattr(self.a, f, 0 if img is None else img.data_ptr())
         self.wt_of = wt
 
+    def route(self, B, Te, Ti):
+        """The form the library takes at these shapes (fusion_route)."""
+        a = self.a
+        a.B, a.Te, a.Ti = B, Te, Ti
+        return fusion_route(a)
+
     def sizes(self, want_dimg, a=None):
         """As ConvCall.sizes: `a` = a forward's argument snapshot (default: the live block)."""
         a = self.a if a is None else a
         key = (a.B, a.Te, a.Ti, a.Di, a.d, a.extra, a.gate, a.image_pre_norm, a.p_img > 0, a.p_txt > 0, a.p_attn > 0,
-               bool(want_dimg))
+               bool(want_dimg), fusion_route(a))
         s = FusionCall._sizes.get(key)
         if s is None:
             oo, nb, sb, mw, sw = (ctypes.c_int64() for _ in range(5))
@@ -934,6 +974,28 @@ def attn_softmax_bwd(P, dPd, Z, H, Tq, Tk, ldS, p=0.0, drop=None, out=None):
     call("mms2ut_attn_softmax_bwd", P.data_ptr(), dPd.data_ptr(), dS.data_ptr(), Z, H, Tq, Tk, ldS,
          None, 0, 0, float(p), seed, off, _s())
     return dS
+
+def attn_softmax_aug(S, Z, Tq, Tk, ldS, q_aug, scale, n_img, u_aug, npad, key_mask=None, extra_key=False,
+                     p=0.0, drop=None):
+    """attn_softmax (H = 1) with the query-side fusion attention's tail columns
+    (mms2ut_attn_softmax_fwd_aug): q_aug / u_aug are column views [rows, >= 2 / npad]."""
+    P = torch.empty_like(S)
+    Pd = torch.empty_like(S) if p > 0 else P
+    seed, off = drop if p > 0 else (0, 0)
+    call("mms2ut_attn_softmax_fwd_aug", S.data_ptr(), P.data_ptr(), Pd.data_ptr(), Z, Tq, Tk, ldS,
+         _p(key_mask), (key_mask.stride(0) if key_mask is not None else 0), int(extra_key), float(p), seed, off,
+         q_aug.data_ptr(), q_aug.stride(0), float(scale), int(n_img), u_aug.data_ptr(), u_aug.stride(0), int(npad),
+         _s())
+    return P, Pd
+
+
+def attn_softmax_bwd_aug(P, dPd, Z, Tq, Tk, ldS, du_aug, scale, n_img, dq_aug, npad, p=0.0, drop=None):
+    """attn_softmax_bwd in place with the tail columns (mms2ut_attn_softmax_bwd_aug)."""
+    seed, off = drop if p > 0 else (0, 0)
+    call("mms2ut_attn_softmax_bwd_aug", P.data_ptr(), dPd.data_ptr(), dPd.data_ptr(), Z, Tq, Tk, ldS, float(p),
+         seed, off, du_aug.data_ptr(), du_aug.stride(0), float(scale), int(n_img), dq_aug.data_ptr(),
+         dq_aug.stride(0), int(npad), _s())
+    return dPd
 
 FLASH_HD = (64, 96, 128)
 

@@ -1096,19 +1096,39 @@ class MMS2UTModel:
             Wo, bo = self.P(pre + ".proj.weight"), self.P(pre + ".proj.bias")
         c["pre"] = pre
         q = K.linear(textd, Wq, bq)
-        kv = K.linear(imgd, Wkv, bkv)                      # [B*Tk, 2d]
-        if extra:
-            bkv_rows = self.params.span(pre + ".bias_k", pre + ".bias_v").view(1, 2 * d)
-            K.copy2d(bkv_rows.expand(B, 2 * d), kv.view(B, Tk * 2 * d)[:, Ti * 2 * d:], B, 2 * d)
-        c["q"], c["kv"] = q, kv
+        c["q"] = q
         key_mask = img_mask  # uint8 [B, >=Tk] prepared by prepare_batch (1 = padded key)
         c["key_mask"] = key_mask
         pat = self._p("SA_attention_dropout")
         c["drop_attn"] = self._drop(pat, B * Te * Tk)
         O = torch.empty(B * Te, d, dtype=F16, device=text.device)
-        c["P"], c["Pd"], c["ldS"] = attn_fwd(q, kv, kv[:, d:], d, 2 * d, 2 * d, B, 1, Te, Tk, d,
-                                             d ** -0.5, O, d, key_mask=key_mask, extra_key=extra,
-                                             p=pat, drop=c["drop_attn"])
+        c["qs"] = self._fusion_call(Di).route(B, Te, Ti)
+        if c["qs"]:
+            # query-side form (csrc/layers.hip): S = scale (q W_k) X^T, O = (Pd X) W_v^T, the biases
+            # and bias_kv in the tail columns of the augmented weights / qk / U
+            R, Dia, ldS, scale = B * Te, K.round_up(Di + 2, 64), K.round_up(Tk, 8), d ** -0.5
+            waug = K.fusion_pack_kv(Wkv, bkv, self.params.span(pre + ".bias_k", pre + ".bias_v") if extra else None, Dia)
+            qk = torch.empty(R, Dia, dtype=F16, device=text.device)
+            K.gemm(q, waug, qk, R, Dia, d, b_kc=False, lda=d, ldb=Dia, ldc=Dia)
+            S = torch.empty(R * ldS, dtype=F16, device=text.device)
+            K.gemm(qk, imgd, S, Te, Tk, Di, lda=Dia, ldb=Di, ldc=ldS, batch=B, sA=(Te * Dia, 0), sB=(Tk * Di, 0),
+                   sC=(Te * ldS, 0), alpha=scale)
+            U = torch.empty(R, Dia, dtype=F16, device=text.device)
+            c["P"], c["Pd"] = K.attn_softmax_aug(S, B, Te, Tk, ldS, qk[:, Di:], scale, Ti, U[:, Di:], Dia - Di,
+                                                 key_mask=key_mask, extra_key=extra, p=pat, drop=c["drop_attn"])
+            K.gemm(c["Pd"], imgd, U, Te, Di, Tk, a_kc=True, b_kc=False, lda=ldS, ldb=Di, ldc=Dia, batch=B,
+                   sA=(Te * ldS, 0), sB=(Tk * Di, 0), sC=(Te * Dia, 0))
+            K.gemm(U, waug[d:], O, R, d, Dia, lda=Dia, ldb=Dia, ldc=d)
+            c["ldS"], c["waug"], c["qk"], c["U"] = ldS, waug, qk, U
+        else:
+            kv = K.linear(imgd, Wkv, bkv)                      # [B*Tk, 2d]
+            if extra:
+                bkv_rows = self.params.span(pre + ".bias_k", pre + ".bias_v").view(1, 2 * d)
+                K.copy2d(bkv_rows.expand(B, 2 * d), kv.view(B, Tk * 2 * d)[:, Ti * 2 * d:], B, 2 * d)
+            c["kv"] = kv
+            c["P"], c["Pd"], c["ldS"] = attn_fwd(q, kv, kv[:, d:], d, 2 * d, 2 * d, B, 1, Te, Tk, d,
+                                                 d ** -0.5, O, d, key_mask=key_mask, extra_key=extra,
+                                                 p=pat, drop=c["drop_attn"])
         c["O"], c["pat"], c["pimg"], c["ptxt"] = O, pat, pimg, ptxt
         if cfg["use_selective_gate"]:
             merge = torch.empty(B * Te, 2 * d, dtype=F16, device=text.device)
@@ -1161,32 +1181,61 @@ class MMS2UTModel:
         K.linear_wgrad(dOp, c["O"], gWo,
                        db=gbo)
         dO = K.linear_dgrad(dOp, Wo)
-        q, kv = c["q"], c["kv"]
+        q = c["q"]
         dq = torch.empty_like(q)
-        dkv = torch.empty_like(kv)
-        attn_bwd(dO, d, q, kv, kv[:, d:], d, 2 * d, 2 * d, c["P"], c["Pd"], c["ldS"], B, 1, Te, Tk, d,
-                 d ** -0.5, dq, dkv, dkv[:, d:], d, 2 * d, 2 * d, p=c["pat"], drop=c["drop_attn"])
-        if extra:
-            # bias_k / bias_v grads = sum over batch of the extra key row; then zero that row
-            rows = dkv.view(B, Tk * 2 * d)[:, Ti * 2 * d:]
-            # on the main stream: the rows are zeroed right after (side-stream race otherwise)
-            K.bias_grad(rows, self.params.span(pre + ".bias_k", pre + ".bias_v", grad=True), side=False)
-            rows.zero_()
-        K.linear_wgrad(dkv, c["imgd"], gWkv,
-                       db=gbkv)
+        need_dx = bool(cfg["image_pre_norm"] or want_dimg)
+        dimgd = None
+        if c["qs"]:
+            R, Dia, ldS, scale = B * Te, c["waug"].shape[1], c["ldS"], d ** -0.5
+            waug, qk, U, imgd, P_, Pd = c["waug"], c["qk"], c["U"], c["imgd"], c["P"], c["Pd"]
+            dU = torch.empty(R, Dia, dtype=F16, device=dres.device)
+            K.gemm(dO, waug[d:], dU, R, Dia, d, b_kc=False, lda=d, ldb=Dia, ldc=Dia)
+            dwa = torch.empty(2 * d, Dia, dtype=F16, device=dres.device)
+            K.linear_wgrad(dO, U, dwa[d:])
+            dPd = torch.empty_like(P_)
+            K.gemm(dU, imgd, dPd, Te, Tk, Di, lda=Dia, ldb=Di, ldc=ldS, batch=B, sA=(Te * Dia, 0), sB=(Tk * Di, 0),
+                   sC=(Te * ldS, 0))
+            dqk = torch.empty(R, Dia, dtype=F16, device=dres.device)
+            K.attn_softmax_bwd_aug(P_, dPd, B, Te, Tk, ldS, dU[:, Di:], scale, Ti, dqk[:, Di:], Dia - Di,
+                                   p=c["pat"], drop=c["drop_attn"])
+            K.gemm(dPd, imgd, dqk, Te, Di, Tk, a_kc=True, b_kc=False, lda=ldS, ldb=Di, ldc=Dia, batch=B,
+                   sA=(Te * ldS, 0), sB=(Tk * Di, 0), sC=(Te * Dia, 0), alpha=scale)
+            K.linear_wgrad(q, dqk, dwa[:d])
+            K.fusion_unpack_kv(dwa, gWkv, gbkv,
+                               self.params.span(pre + ".bias_k", pre + ".bias_v", grad=True) if extra else None)
+            K.gemm(dqk, waug[:d], dq, R, d, Dia, lda=Dia, ldb=Dia, ldc=d)
+            if need_dx:
+                dimgd = torch.empty(B * Tk, Di, dtype=F16, device=dres.device)
+                K.gemm(dPd, qk, dimgd, Tk, Di, Te, a_kc=False, b_kc=False, lda=ldS, ldb=Dia, ldc=Di, batch=B,
+                       sA=(Te * ldS, 0), sB=(Te * Dia, 0), sC=(Tk * Di, 0), alpha=scale)
+                K.gemm(Pd, dU, dimgd, Tk, Di, Te, a_kc=False, b_kc=False, lda=ldS, ldb=Dia, ldc=Di, batch=B,
+                       sA=(Te * ldS, 0), sB=(Te * Dia, 0), sC=(Tk * Di, 0), epi=K.EPI_F16_ACC)
+        else:
+            kv = c["kv"]
+            dkv = torch.empty_like(kv)
+            attn_bwd(dO, d, q, kv, kv[:, d:], d, 2 * d, 2 * d, c["P"], c["Pd"], c["ldS"], B, 1, Te, Tk, d,
+                     d ** -0.5, dq, dkv, dkv[:, d:], d, 2 * d, 2 * d, p=c["pat"], drop=c["drop_attn"])
+            if extra:
+                # bias_k / bias_v grads = sum over batch of the extra key row; then zero that row
+                rows = dkv.view(B, Tk * 2 * d)[:, Ti * 2 * d:]
+                # on the main stream: the rows are zeroed right after (side-stream race otherwise)
+                K.bias_grad(rows, self.params.span(pre + ".bias_k", pre + ".bias_v", grad=True), side=False)
+                rows.zero_()
+            K.linear_wgrad(dkv, c["imgd"], gWkv,
+                           db=gbkv)
+            if need_dx:
+                dimgd = K.linear_dgrad(dkv, Wkv)
         dimg_in = None
         if c["ln_fused"]:
             # image LN gamma/beta grads read dimgd through the key layout + dropout directly
-            dimgd = K.linear_dgrad(dkv, Wkv)
             dimg_in = K.layernorm_bwd(dimgd, c["img_in"], self.P("encoder.image_pre_norm_module.weight"), c["im"],
                                       c["ir"], self.params.span("encoder.image_pre_norm_module.weight",
                                                                 "encoder.image_pre_norm_module.bias", grad=True),
                                       want_dx=want_dimg, dy_grp=Ti if extra else 0, dy_grp_out=Tk if extra else 0,
                                       dy_p=c["pimg"], dy_drop=c["drop_img"])
-        elif cfg["image_pre_norm"] or want_dimg:
-            dimgd = K.linear_dgrad(dkv, Wkv)
+        elif need_dx:
             if extra:
-                dimg = torch.empty(B * Ti, Di, dtype=F16, device=dkv.device)
+                dimg = torch.empty(B * Ti, Di, dtype=F16, device=dimgd.device)
                 K.copy2d(dimgd.view(B, Tk * Di), dimg.view(B, Ti * Di), B, Ti * Di)
             else:
                 dimg = dimgd
