@@ -560,6 +560,121 @@ int mms2ut_noise_mix_f32(float* wave, const int64_t* wave_off, int B,
                          const int16_t* bank, const int64_t* bank_off, int n_clips,
                          const int32_t* params, int n_mix, double* ws, hipStream_t stream);
 
+/* ---------------------------------------------------------------- unit vocoder (CodeHiFiGAN)
+ * Forward-only kernels of fairseq's CodeHiFiGAN generator (csrc/vocoder.hip, vocoder.py).
+ * Activations are time-major fp16 rows [T, C]; C is a multiple of 8 and >= 8 everywhere (16-byte
+ * rows), anything else is refused.  All accumulation is fp32.
+ *
+ * mms2ut_conv1d_tm: implicit-GEMM dilated Conv1d (no im2col image), one launch:
+ *   v[q, co]  = bias[co] + sum_{j < taps, ci} in(x[q + j*dil - pad, ci]) * W[co, ci, j]
+ *               (rows outside [0, T_in) read as zeros; in = leaky-ReLU(in_slope) if in_act)
+ *   v        += res[q, co]                       if res
+ *   v         = leaky-ReLU(v, out_slope)         if out_act
+ *   y[q, co]  = v | scale * v | y[q, co] + scale * v      (acc = NONE | SET | ADD)
+ * w is the weight repacked once at load (vocoder.pack_conv_weight): Cin is cut into slices of
+ * MMS_VOC_CIN_CHUNK; a slice of width cw contributes ceil(taps * cw / 32) K-steps, reduction index
+ * kk = j * cw + ci zero-padded to the step; the image is [K-step][Cout rounded up to 16][32] fp16,
+ * mms2ut_conv1d_tm_packed_halves() elements in all.  (taps - 1) * dil <= MMS_VOC_MAX_SPAN.
+ * The polyphase fields (phases, ostride, ooff, nq, w_phase) are for mms2ut_conv_transpose1d_tm;
+ * a plain convolution passes phases = ostride = 1, ooff = 0, nq = T_out, w_phase = 0.          */
+#define MMS_VOC_CIN_CHUNK 64
+#define MMS_VOC_MAX_SPAN  64
+enum { MMS_VOC_ACC_NONE = 0, MMS_VOC_ACC_SET = 1, MMS_VOC_ACC_ADD = 2 };
+typedef struct {
+  const void* x;        /* fp16 [T_in, Cin], row stride ldx */
+  int64_t ldx;
+  int T_in, Cin;
+  const void* w;        /* packed fp16 weight image(s) */
+  int64_t w_phase;      /* elements between the images of consecutive phases */
+  const float* bias;    /* fp32 [Cout] or NULL */
+  void* y;              /* fp16 [T_out, Cout], row stride ldy */
+  int64_t ldy;
+  int T_out, Cout;
+  int taps, dil, pad;
+  int nq;               /* output indices q in [0, nq) per phase */
+  int phases, ostride, ooff;   /* output row of (q, phase r) = q * ostride + r + ooff */
+  int in_act;
+  float in_slope;
+  const void* res;      /* fp16 [T_out, Cout] or NULL, row stride ldres */
+  int64_t ldres;
+  int acc;              /* MMS_VOC_ACC_* */
+  float scale;
+  int out_act;
+  float out_slope;
+} mms2ut_conv1d_tm_args;
+int mms2ut_conv1d_tm_packed_halves(int Cin, int Cout, int taps, int64_t* out);
+int mms2ut_conv1d_tm(const mms2ut_conv1d_tm_args* a, hipStream_t stream);
+/* ConvTranspose1d(k, stride u, padding p), y[t*u - p + j, co] += in(x[t, ci]) * W[ci, co, j], output
+ * length (T - 1) * u - 2p + k, as u polyphase convolutions in one launch of the kernel above: output
+ * phase r = (t' + p) mod u is a convolution over ceil(k/u) taps.  w_packed holds u images of
+ * mms2ut_conv1d_tm_packed_halves(Cin, Cout, ceil(k/u)) elements each; image r is the packing of
+ * Wr[co, ci, m'] = W[ci, co, r + (ceil(k/u) - 1 - m') * u] (0 where that tap is >= k).           */
+int mms2ut_conv_transpose1d_tm(const void* x, int64_t ldx, int T, int Cin, const void* w_packed,
+                               const float* bias, void* y, int64_t ldy, int Cout, int k, int stride,
+                               int padding, int in_act, float in_slope, hipStream_t stream);
+/* conv_post + tanh (Cout = 1): y[t] = tanh(bias + sum_{j, ci} lrelu(x[t + j - pad, ci]) * w[j, ci]),
+ * w fp32 [taps, Cin], y fp32 [T].                                                               */
+int mms2ut_conv_post_tanh(const void* x, int64_t ldx, int T, int Cin, const float* w, float bias,
+                          int taps, int pad, float in_slope, float* y, hipStream_t stream);
+/* Embedding gather + duration repeat: out[t', :] = dict[codes[src(t')], :] (fp16 [n_embed, D]),
+ * src(t') = the first i with cum[i] > t' (cum: inclusive prefix sum of the durations, int64 [T],
+ * T_out = cum[T - 1]); cum NULL: src(t') = t' and T_out = T.  A code outside [0, n_embed) yields a
+ * zero row.                                                                                     */
+int mms2ut_embed_repeat(const void* dict, int n_embed, int D, const int64_t* codes, int T,
+                        const int64_t* cum, int64_t T_out, void* out, hipStream_t stream);
+/* One layer of fairseq's VariancePredictor in eval mode, fp32 end to end (the rounded durations
+ * must match the fp32 reference): h = LayerNorm(ReLU(Conv1d(x; taps, pad))) over [T, Cout],
+ * taps = 2 * pad + 1.  x fp32 [n_rows, Cin]; idx (int64 [T]) non-NULL: row t of the input is
+ * x[idx[t]] (the embedding lookup), else x has T rows.  w fp32 [taps, Cin, Cout].  proj_w NULL:
+ * h is written to out (fp32 [T, Cout]).  proj_w (fp32 [Cout]) non-NULL: the last layer,
+ * logd[t] = h[t] . proj_w + proj_b and dur[t] = max(round_half_even(exp(logd[t]) - 1), 1).     */
+int mms2ut_var_pred_layer_f32(const float* x, const int64_t* idx, int n_rows, int T, int Cin,
+                              const float* w, const float* b, int taps, int pad, int Cout,
+                              const float* ln_g, const float* ln_b, float eps, float* out,
+                              const float* proj_w, float proj_b, float* logd, int32_t* dur,
+                              hipStream_t stream);
+/* The whole generator for one utterance in one call (fairseq CodeGenerator.forward without speaker
+ * or f0 inputs): embedding gather + duration repeat, conv_pre, per stage the transposed conv and
+ * its nk ResBlocks (x = sum_j ResBlock_j(x) / nk), conv_post + tanh -- the launches a caller would
+ * issue through the entry points above, in the same order with the same arguments (the result is
+ * bit-identical), without a host round trip per launch.  A conv of a ResBlock: kernel k (odd),
+ * dilation dil, padding dil (k - 1) / 2.  ups[i]: ConvTranspose1d(k, stride u, padding (k - u) / 2),
+ * weights packed as mms2ut_conv_transpose1d_tm wants them; every other weight as mms2ut_conv1d_tm.
+ * T_frames: the rows after the duration repeat (cum[T - 1], or T with cum NULL).
+ * mms2ut_hifigan_sizes: ws_halves = fp16 elements of the caller-owned workspace, T_wave = the
+ * samples written to wave (fp32).  launches (may be NULL) receives the number of kernel launches. */
+#define MMS_VOC_MAX_STAGES    8
+#define MMS_VOC_MAX_RESBLOCKS 4
+#define MMS_VOC_MAX_DILS      4
+typedef struct {
+  const void* w;        /* packed fp16 */
+  const float* b;       /* fp32 [Cout] */
+  int k, dil;
+} mms2ut_voc_conv;
+typedef struct {
+  const void* w;
+  const float* b;
+  int k, u, cout;
+} mms2ut_voc_up;
+typedef struct {
+  const void* dict;     /* fp16 [n_embed, D] */
+  int n_embed, D;
+  int C0;               /* conv_pre's output channels (upsample_initial_channel) */
+  int n_stages, nk;
+  int nd[MMS_VOC_MAX_RESBLOCKS];                 /* dilations of ResBlock j */
+  mms2ut_voc_conv pre;
+  mms2ut_voc_up ups[MMS_VOC_MAX_STAGES];
+  mms2ut_voc_conv c1[MMS_VOC_MAX_STAGES][MMS_VOC_MAX_RESBLOCKS][MMS_VOC_MAX_DILS];
+  mms2ut_voc_conv c2[MMS_VOC_MAX_STAGES][MMS_VOC_MAX_RESBLOCKS][MMS_VOC_MAX_DILS];
+  const float* post_w;  /* fp32 [post_k, C_last] */
+  float post_b;
+  int post_k;
+  float slope, post_slope;                       /* 0.1 and 0.01 in fairseq */
+} mms2ut_hifigan;
+int mms2ut_hifigan_sizes(const mms2ut_hifigan* m, int64_t T_frames, int64_t* ws_halves, int64_t* T_wave);
+int mms2ut_hifigan_fwd(const mms2ut_hifigan* m, const int64_t* codes, int T, const int64_t* cum,
+                       int64_t T_frames, void* ws, float* wave, int* launches, hipStream_t stream);
+
 /* ---------------------------------------------------------------- transformer layers
  * One whole pre-LN transformer layer per call — SURVEY §8b "encoder / decoder layer fwd/bwd":
  *   MMS_LAYER_ENC: fairseq TransformerEncoderLayer (encoder_normalize_before; A5, reached from

@@ -128,6 +128,39 @@ class LayerGradArgs(C.Structure):
 
 LAYER_GRAD_ARGS = _packer(LayerGradArgs)
 
+VOC_CIN_CHUNK, VOC_MAX_SPAN = 64, 64                     # include/mms2ut.h MMS_VOC_*
+VOC_ACC_NONE, VOC_ACC_SET, VOC_ACC_ADD = range(3)
+
+
+class Conv1dTmArgs(C.Structure):
+    """mms2ut_conv1d_tm_args (include/mms2ut.h): one implicit-GEMM Conv1d launch of the vocoder."""
+    _fields_ = [("x", vp), ("ldx", i64), ("T_in", i32), ("Cin", i32), ("w", vp), ("w_phase", i64), ("bias", vp),
+                ("y", vp), ("ldy", i64), ("T_out", i32), ("Cout", i32), ("taps", i32), ("dil", i32), ("pad", i32),
+                ("nq", i32), ("phases", i32), ("ostride", i32), ("ooff", i32), ("in_act", i32), ("in_slope", f32),
+                ("res", vp), ("ldres", i64), ("acc", i32), ("scale", f32), ("out_act", i32), ("out_slope", f32)]
+
+
+CONV1D_TM_ARGS = _packer(Conv1dTmArgs)
+
+VOC_MAX_STAGES, VOC_MAX_RESBLOCKS, VOC_MAX_DILS = 8, 4, 4   # include/mms2ut.h MMS_VOC_MAX_*
+
+
+class VocConv(C.Structure):
+    _fields_ = [("w", vp), ("b", vp), ("k", i32), ("dil", i32)]
+
+
+class VocUp(C.Structure):
+    _fields_ = [("w", vp), ("b", vp), ("k", i32), ("u", i32), ("cout", i32)]
+
+
+class HifiGan(C.Structure):
+    """mms2ut_hifigan (include/mms2ut.h): the generator's weights for mms2ut_hifigan_fwd."""
+    _fields_ = [("dict", vp), ("n_embed", i32), ("D", i32), ("C0", i32), ("n_stages", i32), ("nk", i32),
+                ("nd", i32 * VOC_MAX_RESBLOCKS), ("pre", VocConv), ("ups", VocUp * VOC_MAX_STAGES),
+                ("c1", VocConv * VOC_MAX_DILS * VOC_MAX_RESBLOCKS * VOC_MAX_STAGES),
+                ("c2", VocConv * VOC_MAX_DILS * VOC_MAX_RESBLOCKS * VOC_MAX_STAGES),
+                ("post_w", vp), ("post_b", f32), ("post_k", i32), ("slope", f32), ("post_slope", f32)]
+
 
 # name -> (restype, argtypes); every symbol include/mms2ut.h declares
 SIGNATURES = {
@@ -218,6 +251,15 @@ SIGNATURES = {
     "mms2ut_fbank_cmvn_collate": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "mms2ut_specaugment_f16": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, vp]),
     "mms2ut_noise_mix_f32": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]),
+    "mms2ut_conv1d_tm_packed_halves": (i32, [i32, i32, i32, C.POINTER(C.c_int64)]),
+    "mms2ut_conv1d_tm": (i32, [vp, vp]),   # CONV1D_TM_ARGS.pack(...) bytes
+    "mms2ut_conv_transpose1d_tm": (i32, [vp, i64, i32, i32, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp]),
+    "mms2ut_conv_post_tanh": (i32, [vp, i64, i32, i32, vp, f32, i32, i32, f32, vp, vp]),
+    "mms2ut_embed_repeat": (i32, [vp, i32, i32, vp, i32, vp, i64, vp, vp]),
+    "mms2ut_var_pred_layer_f32": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, f32, vp, vp, f32,
+                                        vp, vp, vp]),
+    "mms2ut_hifigan_sizes": (i32, [vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mms2ut_hifigan_fwd": (i32, [vp, vp, i32, vp, i64, vp, vp, C.POINTER(C.c_int), vp]),
     "mms2ut_layer_arena": (i32, [vp, vp, vp]),
     "mms2ut_layer_scratch": (i32, [vp, f32, vp, vp]),
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),

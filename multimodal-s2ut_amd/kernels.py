@@ -1382,4 +1382,149 @@ def round_up(x, m):
     return (x + m - 1) // m * m
 
 
+# ============================================================================ unit vocoder
+
+def conv1d_tm_packed_halves(Cin, Cout, taps):
+    """Elements of the packed weight image of one conv1d_tm problem (vocoder.pack_conv_weight)."""
+    n = ctypes.c_int64(0)
+    call("mms2ut_conv1d_tm_packed_halves", int(Cin), int(Cout), int(taps), ctypes.byref(n))
+    return n.value
+
+
+def _rows16(t, name):
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name}: time-major [T, C] rows expected, got {tuple(t.shape)} strides {t.stride()}")
+
+
+def conv1d_tm(x, w_packed, bias, Cout, taps, dil=1, pad=None, *, in_slope=None, res=None, out_slope=None,
+              acc=_lib.VOC_ACC_NONE, scale=1.0, out=None):
+    """Implicit-GEMM Conv1d over time-major fp16 rows: x [T, Cin] -> [T + 2 pad - dil (taps - 1), Cout].
+    in_slope / out_slope: leaky-ReLU on the input as it is read / on the result; res: + res[t] before the
+    output activation; acc SET / ADD: out = scale * v / out += scale * v (out required for ADD)."""
+    _chk(x)
+    _chk(w_packed)
+    _rows16(x, "conv1d_tm x")
+    T, Cin = x.shape
+    pad = dil * (taps - 1) // 2 if pad is None else pad
+    T_out = T + 2 * pad - dil * (taps - 1)
+    if T_out < 1:
+        raise ValueError(f"conv1d_tm: empty output (T {T}, taps {taps}, dilation {dil}, pad {pad})")
+    if Cin % 8 == 0 and Cin >= 8 and Cout % 8 == 0 and Cout >= 8 and \
+            w_packed.numel() != conv1d_tm_packed_halves(Cin, Cout, taps):
+        raise ValueError(f"conv1d_tm: packed weight of {w_packed.numel()} elements for Cin {Cin}, Cout {Cout}, taps {taps}")
+    if out is None:
+        if acc == _lib.VOC_ACC_ADD:
+            raise ValueError("conv1d_tm: acc ADD needs the tensor to add into")
+        out = torch.empty(T_out, Cout, dtype=F16, device=x.device)
+    _chk(out)
+    _rows16(out, "conv1d_tm out")
+    if tuple(out.shape) != (T_out, Cout):
+        raise ValueError(f"conv1d_tm: out {tuple(out.shape)}, expected {(T_out, Cout)}")
+    if bias is not None:
+        _chk(bias, torch.float32)
+        assert bias.numel() == Cout and bias.is_contiguous()
+    if res is not None:
+        _chk(res)
+        _rows16(res, "conv1d_tm res")
+        if tuple(res.shape) != (T_out, Cout):
+            raise ValueError(f"conv1d_tm: res {tuple(res.shape)}, expected {(T_out, Cout)}")
+    call("mms2ut_conv1d_tm", _lib.CONV1D_TM_ARGS.pack(
+        x.data_ptr(), x.stride(0), T, Cin, w_packed.data_ptr(), 0, _p(bias) or 0, out.data_ptr(), out.stride(0),
+        T_out, Cout, taps, dil, pad, T_out, 1, 1, 0, int(in_slope is not None), float(in_slope or 0.0),
+        _p(res) or 0, res.stride(0) if res is not None else 0, int(acc), float(scale),
+        int(out_slope is not None), float(out_slope or 0.0)), _s())
+    return out
+
+
+def conv_transpose1d_tm(x, w_packed, bias, Cout, k, stride, padding, *, in_slope=None, out=None):
+    """ConvTranspose1d over time-major fp16 rows as `stride` polyphase convolutions in one launch:
+    x [T, Cin] -> [(T - 1) stride - 2 padding + k, Cout]; w_packed from vocoder.pack_conv_transpose_weight."""
+    _chk(x)
+    _chk(w_packed)
+    _rows16(x, "conv_transpose1d_tm x")
+    T, Cin = x.shape
+    T_out = (T - 1) * stride - 2 * padding + k
+    if T_out < 1:
+        raise ValueError(f"conv_transpose1d_tm: empty output (T {T}, k {k}, stride {stride}, padding {padding})")
+    taps = -(-k // stride)
+    if Cin % 8 == 0 and Cin >= 8 and Cout % 8 == 0 and Cout >= 8 and \
+            w_packed.numel() != stride * conv1d_tm_packed_halves(Cin, Cout, taps):
+        raise ValueError(f"conv_transpose1d_tm: packed weight of {w_packed.numel()} elements for Cin {Cin}, "
+                         f"Cout {Cout}, k {k}, stride {stride}")
+    if out is None:
+        out = torch.empty(T_out, Cout, dtype=F16, device=x.device)
+    _chk(out)
+    _rows16(out, "conv_transpose1d_tm out")
+    if tuple(out.shape) != (T_out, Cout):
+        raise ValueError(f"conv_transpose1d_tm: out {tuple(out.shape)}, expected {(T_out, Cout)}")
+    if bias is not None:
+        _chk(bias, torch.float32)
+        assert bias.numel() == Cout and bias.is_contiguous()
+    call("mms2ut_conv_transpose1d_tm", x.data_ptr(), x.stride(0), T, Cin, w_packed.data_ptr(), _p(bias),
+         out.data_ptr(), out.stride(0), Cout, k, stride, padding, int(in_slope is not None), float(in_slope or 0.0),
+         _s())
+    return out
+
+
+def conv_post_tanh(x, w, bias, pad, in_slope):
+    """fp32 [T] = tanh(bias + Conv1d(leaky_relu(x, in_slope)) to one channel); w fp32 [taps, Cin]."""
+    _chk(x)
+    _chk(w, torch.float32)
+    _rows16(x, "conv_post_tanh x")
+    T, Cin = x.shape
+    assert w.is_contiguous() and w.shape[1] == Cin
+    y = torch.empty(T, dtype=torch.float32, device=x.device)
+    call("mms2ut_conv_post_tanh", x.data_ptr(), x.stride(0), T, Cin, w.data_ptr(), float(bias), w.shape[0], int(pad),
+         float(in_slope), y.data_ptr(), _s())
+    return y
+
+
+def embed_repeat(table, codes, cum=None, T_out=None):
+    """fp16 [T_out, D]: row t' = table[codes[src(t')]]; cum = inclusive prefix sum of the durations
+    (int64 [T], T_out = its last element) or None for src(t') = t'."""
+    _chk(table)
+    _chk(codes, torch.int64)
+    assert table.is_contiguous() and codes.is_contiguous() and codes.dim() == 1
+    T = codes.numel()
+    if cum is None:
+        T_out = T
+    else:
+        _chk(cum, torch.int64)
+        assert cum.is_contiguous() and cum.numel() == T and T_out is not None
+    out = torch.empty(int(T_out), table.shape[1], dtype=F16, device=table.device)
+    call("mms2ut_embed_repeat", table.data_ptr(), table.shape[0], table.shape[1], codes.data_ptr(), T, _p(cum),
+         int(T_out), out.data_ptr(), _s())
+    return out
+
+
+def var_pred_layer(x, w, b, ln_g, ln_b, *, idx=None, proj=None, eps=1e-5):
+    """One fp32 VariancePredictor layer LayerNorm(ReLU(Conv1d(x))) -> fp32 [T, Cout]; w fp32
+    [taps, Cin, Cout].  idx: int64 [T] row indices into x (the embedding lookup).  proj = (w [Cout],
+    b): the last layer, returns (logd fp32 [T], dur int32 [T])."""
+    for t in (x, w, b, ln_g, ln_b):
+        _chk(t, torch.float32)
+        assert t.is_contiguous()
+    taps, Cin, Cout = w.shape
+    assert x.shape[1] == Cin and taps % 2 == 1
+    T = x.shape[0]
+    if idx is not None:
+        _chk(idx, torch.int64)
+        assert idx.is_contiguous()
+        T = idx.numel()
+    out = logd = dur = pw = None
+    pb = 0.0
+    if proj is None:
+        out = torch.empty(T, Cout, dtype=torch.float32, device=x.device)
+    else:
+        pw, pb = proj
+        _chk(pw, torch.float32)
+        assert pw.is_contiguous() and pw.numel() == Cout
+        logd = torch.empty(T, dtype=torch.float32, device=x.device)
+        dur = torch.empty(T, dtype=torch.int32, device=x.device)
+    call("mms2ut_var_pred_layer_f32", x.data_ptr(), _p(idx), x.shape[0], T, Cin, w.data_ptr(), b.data_ptr(), taps,
+         taps // 2, Cout, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), _p(out), _p(pw), float(pb), _p(logd), _p(dur),
+         _s())
+    return out if proj is None else (logd, dur)
+
+
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]

@@ -274,6 +274,18 @@ class MultiModalSpeechToSpeechTask:
                                      len_penalty=getattr(args, "lenpen", 1.0),
                                      min_len=getattr(args, "min_len", 1))
 
+    def build_vocoder(self, args=None, device="cuda"):
+        """The data config's ``vocoder: {type: code_hifigan, checkpoint, config}`` mapping (fairseq
+        S2SDataConfig.vocoder) -> vocoder.CodeHiFiGAN; None when the config has no such mapping."""
+        from . import manifest as M
+        from .vocoder import vocoder_from_data_config
+        a = args if args is not None else self.args
+        data = getattr(a, "data", None)
+        if not data:
+            return None
+        data_cfg = M.load_data_config(os.path.join(data, getattr(a, "config_yaml", None) or "config.yaml"))
+        return vocoder_from_data_config(data_cfg, root=data, device=device)
+
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         if prefix_tokens is not None or constraints is not None:
             raise NotImplementedError("prefix tokens / constraints in beam search")
