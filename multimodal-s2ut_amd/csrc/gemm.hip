@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 
 #include "gemm_common.h"
 
@@ -215,11 +216,21 @@ MMS_DEV void dma_gemm_tile(const GemmP& P, char* smem, int z, int tm, int tn) {
   const int nk = (kend - kbeg + BK - 1) / BK;
   // k offset of stage t relative to the descriptor base
   auto k_rel = [&](int t, bool kc) { return kc ? kbeg + t * BK : t * BK; };
+  // NT, fp16 output, register epilogue: weight rows permuted (gemm_common.h perm_epilogue); launch-uniform
+  constexpr bool PERM_T = A_KC && B_KC && !RS && epi_perm<EPI>();
+  const bool perm = PERM_T && reg_epilogue_ok(P);
+  char* Cz;
+  if (EPI == MMS_EPI_F32)
+    Cz = reinterpret_cast<char*>(P.C) + (z1 * P.sC1 + z2 * P.sC2 + zs * P.sCsplit) * 4;
+  else
+    Cz = reinterpret_cast<char*>(P.C) + (z1 * P.sC1 + z2 * P.sC2) * 2;
+  const h16* auxz = P.aux ? P.aux + z1 * P.sX1 + z2 * P.sX2 : nullptr;
+  PermOperands<EPI, 4> op;
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s) {
     if (s < nk) {
       dma_tile<A_KC>(ra, SA(s), P.lda, bm, k_rel(s, A_KC), wid, lane);
-      dma_tile<B_KC>(rb, SB(s), P.ldb, bn, k_rel(s, B_KC), wid, lane);
+      dma_tile<B_KC>(rb, SB(s), P.ldb, bn, k_rel(s, B_KC), wid, lane, perm);
     }
   }
   // An MN-contiguous operand is read with ds_read_b64_tr_b16, and the compiler cannot tell those
@@ -234,17 +245,24 @@ MMS_DEV void dma_gemm_tile(const GemmP& P, char* smem, int z, int tm, int tn) {
   // All 16 fragments of the stage are read before its MFMAs (the second k-half's reads no longer
   // wait behind the first half's MFMAs): 0-5 % faster isolated on the step's NT shapes, step flat
   // (profiles/round3_v5_gemm_read_all_ab.txt).
-  for (int kt = 0; kt < nk; ++kt) {
+  // One k-step.  With the permuted epilogue the last step is peeled off the loop (LAST): it waits for
+  // vmcnt(0) and issues no DMA, so the epilogue's row operands are loaded behind its barrier — under
+  // its 64 MFMAs, with no counted wait of the ring after them — whatever the number of k-steps.
+  auto k_step = [&](int kt, auto last_tag) {
+    constexpr bool LAST = decltype(last_tag)::value;
     // stage kt must have landed; leave the younger stages (issued earlier) in flight
     const int younger = min(STAGES - 2, nk - 1 - kt);
     if (STAGES >= 3 && younger >= 1) wait_vm<8>(); else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     const int nxt = kt + STAGES - 1;
     const int cur = kt % STAGES;
+    if constexpr (PERM_T && LAST) {
+      if (perm) perm_prefetch<EPI, 4>(P, op, bm, bn, wm, wn, lane, Cz, auxz);
+    }
     if (!READ_FIRST && nxt < nk) {
       const int sb = nxt % STAGES;
       dma_tile<A_KC>(ra, SA(sb), P.lda, bm, k_rel(nxt, A_KC), wid, lane);
-      dma_tile<B_KC>(rb, SB(sb), P.ldb, bn, k_rel(nxt, B_KC), wid, lane);
+      dma_tile<B_KC>(rb, SB(sb), P.ldb, bn, k_rel(nxt, B_KC), wid, lane, perm);
     }
     h16x8 fa2[2][4], fb2[2][4];
     {
@@ -259,7 +277,7 @@ MMS_DEV void dma_gemm_tile(const GemmP& P, char* smem, int z, int tm, int tn) {
     if (READ_FIRST && nxt < nk) {
       const int sb = nxt % STAGES;
       dma_tile<A_KC>(ra, SA(sb), P.lda, bm, k_rel(nxt, A_KC), wid, lane);
-      dma_tile<B_KC>(rb, SB(sb), P.ldb, bn, k_rel(nxt, B_KC), wid, lane);
+      dma_tile<B_KC>(rb, SB(sb), P.ldb, bn, k_rel(nxt, B_KC), wid, lane, perm);
     }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
@@ -278,6 +296,13 @@ MMS_DEV void dma_gemm_tile(const GemmP& P, char* smem, int z, int tm, int tn) {
         for (int i = 0; i < 4; ++i) rs[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, fa[i], rs[i], 0, 0, 0);
       }
     }
+  };
+  if constexpr (PERM_T) {
+    for (int kt = 0; kt < nk - 1; ++kt) k_step(kt, std::false_type{});
+    if (nk > 0) k_step(nk - 1, std::true_type{});
+    else if (perm) perm_prefetch<EPI, 4>(P, op, bm, bn, wm, wn, lane, Cz, auxz);
+  } else {
+    for (int kt = 0; kt < nk; ++kt) k_step(kt, std::false_type{});
   }
 #undef SA
 #undef SB
@@ -291,22 +316,25 @@ MMS_DEV void dma_gemm_tile(const GemmP& P, char* smem, int z, int tm, int tn) {
       }
     }
   }
-  char* Cz;
-  if (EPI == MMS_EPI_F32)
-    Cz = reinterpret_cast<char*>(P.C) + (z1 * P.sC1 + z2 * P.sC2 + zs * P.sCsplit) * 4;
-  else
-    Cz = reinterpret_cast<char*>(P.C) + (z1 * P.sC1 + z2 * P.sC2) * 2;
-  const h16* auxz = P.aux ? P.aux + z1 * P.sX1 + z2 * P.sX2 : nullptr;
   // the ring is idle once every wave is past its last fragment read (no DMA is in flight: the
   // last k-step waited for vmcnt(0))
+#if MMS_GEMM_PERM_DIRECT   // A/B: direct stores use no LDS, so no barrier in front of them
+  if (!perm)
+#endif
   __syncthreads();
-#ifdef MMS_GEMM_NOEPI   // ablation build: no epilogue (accumulators kept live; garbage output)
+#ifdef MMS_GEMM_NOEPI  // ablation build: no epilogue (accumulators kept live; garbage output)
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) asm volatile("" :: "v"(acc[i][j]));
   (void)Cz; (void)auxz;
 #else
+  if constexpr (PERM_T) {
+    if (perm) {   // launch-uniform
+      perm_epilogue<EPI, 4, 64 * 64 * 4>(P, smem, acc, op, bm, bn, wm, wn, wid, lane, Cz, auxz);
+      return;
+    }
+  }
   staged_epilogue<EPI>(P, smem, acc, bm, bn, wm, wn, wid, lane, Cz, auxz);
 #endif
 }
@@ -329,7 +357,8 @@ __global__ void __launch_bounds__(NT, (STAGES <= 2 ? 2 : 1)) gemm_dma_kernel(Gem
 // 128x128 tiles (e.g. M = 11-16 k rows x N = 768: 564 tiles of 128 rows for 512 block slots, a
 // second round for 52 of them) taller tiles fit fewer rounds at 1.25x / 1.5x the work per tile;
 // 96-row tiles fill a short single round better.  Same k order, same MFMA operands per
-// accumulator, same staged epilogue per element: bit-identical to gemm_dma_kernel<true, true, EPI, 2>.
+// accumulator, same epilogue per element (permuted register form or staged, chosen per launch as
+// there): bit-identical to gemm_dma_kernel<true, true, EPI, 2>.
 // ------------------------------------------------------------------------------------------
 template <int EPI, int FRT>
 __global__ void __launch_bounds__(NT, 2) gemm_tall_kernel(GemmP P, int tiles_m, int tiles_n, int total) {
@@ -371,18 +400,29 @@ __global__ void __launch_bounds__(NT, 2) gemm_tall_kernel(GemmP P, int tiles_m, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nk = P.K / BK;   // K % 64 == 0 (host)
+  // weight rows permuted for the register epilogue on whole 16-B runs (gemm_common.h perm_epilogue)
+  constexpr bool PERM_T = epi_perm<EPI>() && MMS_GEMM_REG_TALL;
+  const bool perm = PERM_T && reg_epilogue_ok(P);   // launch-uniform
+  constexpr int WR = 16 * FRT, F1 = FRT < 4 ? FRT : 4;
+  PermOperands<EPI, FRT> op;
   if (nk > 0) {
     dma_a(SA(0), 0);
-    dma_tile<true>(rb, SB(0), P.ldb, bn, 0, wid, lane);
+    dma_tile<true>(rb, SB(0), P.ldb, bn, 0, wid, lane, perm);
   }
   constexpr bool PR = PRIO && EPI != MMS_EPI_F32;
-  for (int kt = 0; kt < nk; ++kt) {
+  // one k-step; the last is peeled off the loop when the epilogue's row operands are prefetched
+  // under it (it issues no DMA and nothing after it waits on the ring by count)
+  auto k_step = [&](int kt, auto last_tag) {
+    constexpr bool LAST = decltype(last_tag)::value;
     wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     const int cur = kt & 1;
+    if constexpr (PERM_T && LAST) {
+      if (perm) perm_prefetch<EPI, FRT>(P, op, bm + (WR - 64) * wm, bn, wm, wn, lane, P.C, P.aux);
+    }
     if (kt + 1 < nk) {
       dma_a(SA(cur ^ 1), (kt + 1) * BK);
-      dma_tile<true>(rb, SB(cur ^ 1), P.ldb, bn, (kt + 1) * BK, wid, lane);
+      dma_tile<true>(rb, SB(cur ^ 1), P.ldb, bn, (kt + 1) * BK, wid, lane, perm);
     }
     h16x8 fa2[2][FRT], fb2[2][4];
 #pragma unroll
@@ -402,14 +442,30 @@ __global__ void __launch_bounds__(NT, 2) gemm_tall_kernel(GemmP P, int tiles_m, 
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb2[kk][j], fa2[kk][i], acc[i][j], 0, 0, 0);
       if (PR) __builtin_amdgcn_s_setprio(0);
     }
+  };
+  if constexpr (PERM_T) {
+    for (int kt = 0; kt < nk - 1; ++kt) k_step(kt, std::false_type{});
+    if (nk > 0) k_step(nk - 1, std::true_type{});
+    else if (perm) perm_prefetch<EPI, FRT>(P, op, bm + (WR - 64) * wm, bn, wm, wn, lane, P.C, P.aux);
+  } else {
+    for (int kt = 0; kt < nk; ++kt) k_step(kt, std::false_type{});
   }
 #undef SA
 #undef SB
+#if MMS_GEMM_PERM_DIRECT   // A/B: direct stores use no LDS, so no barrier in front of them
+  if (!perm)
+#endif
   __syncthreads();   // the ring is idle (the last k-step waited for vmcnt(0))
   // the wave's rows [bm + 16 FRT wm, + 16 FRT): fragments 0-3 (64 rows), then the rest, each
   // through the wave's 16 KiB staging area (staged_epilogue places wave rows at bm + 64 wm)
-  constexpr int WR = 16 * FRT, F1 = FRT < 4 ? FRT : 4;
-  if constexpr (epi_regs<EPI>() && MMS_GEMM_REG_TALL) {   // all FRT fragments in one pass (fp16 slots: 2 KiB per fragment)
+  if constexpr (PERM_T) {   // all FRT fragments in one pass (fp16 slots: 2 KiB per fragment)
+    if (perm) {
+      perm_epilogue<EPI, FRT, FRT * 2048>(P, smem, acc, op, bm + (WR - 64) * wm, bn, wm, wn, wid, lane, P.C, P.aux);
+      stamp_end(P.stamps, t_start);
+      return;
+    }
+  }
+  if constexpr (epi_regs<EPI>() && MMS_GEMM_REG_TALL) {   // (without MMS_GEMM_PERM) the unpermuted register epilogue
     if (reg_epilogue_ok(P)) {
       reg_epilogue<EPI, FRT, FRT * 2048>(P, smem, acc, bm + (WR - 64) * wm, bn, wm, wn, wid, lane, P.C);
       stamp_end(P.stamps, t_start);

@@ -336,7 +336,9 @@ constexpr bool epi_drops() {
 // LDS slot (FR x 16 rows x 128 B, half the bytes of the fp32 staging, one pass for up to 8 fragments)
 // and come back row-major for 16-B stores of whole 128-B row segments.  Same per-element arithmetic
 // and the same dropout counters as the staged path: bit-identical.  The slot is written and read by
-// one wave only, so no workgroup barrier sits between the two.
+// one wave only, so no workgroup barrier sits between the two.  The NT LDS-DMA kernels use the
+// permuted form below (perm_epilogue), which also carries the operand-reading epilogues; this one
+// serves the kernels whose weight rows are not permuted (register-staged, 256x256, TN / NN, grouped).
 #ifndef MMS_GEMM_REG_EPI
 #define MMS_GEMM_REG_EPI 1
 #endif
@@ -444,6 +446,217 @@ MMS_DEV void reg_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4],
     const int m = bm + wm * 64 + rr;
     if (m < P.M) *reinterpret_cast<u32x4_*>(C + (long)m * P.ldc + n) = v;
   }
+}
+
+// Permuted register epilogue: the NT LDS-DMA kernels (gemm_dma_kernel<true, true>, gemm_tall_kernel)
+// fill LDS row 16 j + 4 g + e of a wave's 64-row strip of the weight from weight row
+//   c(j, g, e) = 32 (j >> 1) + 8 g + 4 (j & 1) + e        (perm_row: a rotation of bits 2-4)
+// of that strip (the source address of the DMA is per lane, the LDS image and the fragment reads do
+// not change).  Accumulator (j, g, e) is then output column c(j, g, e): per row a lane owns columns
+// 32 h + 8 g .. + 7 (h = 0, 1: accumulators 2 h and 2 h + 1), two whole 16-B runs, so the epilogues
+// that read a row operand (residual, pre-activation, gate, accumulated C) load it straight into the
+// MFMA layout with 16-B loads — issued under the last k-step (perm_prefetch), not behind the k-loop
+// and a barrier — and the element math runs on the accumulators.  Same expressions, fp32 -> fp16
+// rounding points and dropout counters (offset + m ld_rng + n of the element's true (m, n)) as the
+// staged path: bit-identical.  Launch-uniform choice (reg_epilogue_ok), as for reg_epilogue.
+#ifndef MMS_GEMM_PERM
+#define MMS_GEMM_PERM 1
+#endif
+// A/B: the two 16-B runs of a lane stored straight from the MFMA layout (16 rows x 64 B per
+// instruction, no LDS) instead of through the wave's fp16 slot (whole 128-B row segments)
+#ifndef MMS_GEMM_PERM_DIRECT
+#define MMS_GEMM_PERM_DIRECT 0
+#endif
+template <int EPI>
+constexpr bool epi_perm() {
+  return MMS_GEMM_REG_EPI && MMS_GEMM_PERM &&
+         (EPI == MMS_EPI_F16 || EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GATE ||
+          EPI == MMS_EPI_RELU_DROP_BWD || EPI == MMS_EPI_F16_ACC);
+}
+MMS_DEV int perm_row(int r) { return (r & ~0x1c) | ((r & 0x0c) << 1) | ((r & 0x10) >> 2); }
+
+// a wave's row operands in the MFMA layout: [i][h] = row 16 i + (l & 15), columns 32 h + 8 (l >> 4) .. + 7
+template <int EPI, int FR>
+struct PermOperands {
+  h16x8 ax[FR][2];                              // aux row / existing C
+  h16x8 ax2[EPI == MMS_EPI_GATE ? FR : 1][2];   // GATE: aux + N
+  h16x8 bias[2];
+};
+
+// GATE on a tall tile (FR > 4) loads its two operands in the epilogue instead, one fragment ahead of
+// the math: 2 x 2 FR operand vectors beside the k-step's fragments, or beside the epilogue's
+// temporaries, spill (192-row tiles)
+template <int EPI, int FR>
+constexpr bool perm_gate_late() { return EPI == MMS_EPI_GATE && FR > 4; }
+
+// rows bm + 64 wm + 16 i + (l & 15), columns bn + 64 wn ..+ 64 (as reg_epilogue); zero where there is
+// nothing to read (rows past M, no bias, a wave whose columns lie past N)
+template <int EPI, int FR>
+MMS_DEV void perm_prefetch(const GemmP& P, PermOperands<EPI, FR>& op, int bm, int bn, int wm, int wn, int lane,
+                           const void* Cz, const h16* auxz) {
+  h16x8 z8;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) z8[e] = (h16)0.f;
+  constexpr bool LOADS = (EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GATE || EPI == MMS_EPI_RELU_DROP_BWD ||
+                          EPI == MMS_EPI_F16_ACC) && !perm_gate_late<EPI, FR>();
+  op.bias[0] = op.bias[1] = z8;
+#pragma unroll
+  for (int i = 0; i < FR; ++i) op.ax[i][0] = op.ax[i][1] = z8;
+#pragma unroll
+  for (int i = 0; i < (EPI == MMS_EPI_GATE ? FR : 1); ++i) op.ax2[i][0] = op.ax2[i][1] = z8;
+  if (bn + wn * 64 >= P.N) return;   // wave-uniform
+  const int m0 = bm + wm * 64 + (lane & 15), nw = bn + wn * 64 + 8 * (lane >> 4);
+  if (EPI != MMS_EPI_RELU_DROP_BWD && P.bias) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) op.bias[h] = *reinterpret_cast<const h16x8*>(P.bias + nw + 32 * h);
+  }
+  if (LOADS) {
+    const h16* src = EPI == MMS_EPI_F16_ACC ? reinterpret_cast<const h16*>(Cz) : auxz;
+    const long ld = EPI == MMS_EPI_F16_ACC ? P.ldc : P.ldaux;
+#pragma unroll
+    for (int i = 0; i < FR; ++i) {
+      const int m = m0 + 16 * i;
+      if (m < P.M) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          op.ax[i][h] = *reinterpret_cast<const h16x8*>(src + (long)m * ld + nw + 32 * h);
+          if (EPI == MMS_EPI_GATE)
+            op.ax2[EPI == MMS_EPI_GATE ? i : 0][h] = *reinterpret_cast<const h16x8*>(src + (long)m * ld + P.N + nw + 32 * h);
+        }
+      }
+    }
+  }
+}
+
+// caller: reg_epilogue_ok(P), the weight rows permuted, op from perm_prefetch with the same arguments
+template <int EPI, int FR, int SLOTB>
+MMS_DEV void perm_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4], PermOperands<EPI, FR>& op,
+                           int bm, int bn, int wm, int wn, int wid, int lane, void* Cz, const h16* auxz) {
+  static_assert(SLOTB >= FR * 2048, "staging slot too small");
+  if (bn + wn * 64 >= P.N) return;   // wave-uniform: all 64 columns past N
+  // GATE on a tall tile: fragment i + 1's operands are loaded ahead of fragment i's math (by themselves
+  // the loads cannot move up past the previous fragment's out2 stores)
+  constexpr bool GATE_LATE = perm_gate_late<EPI, FR>();
+  h16x8 nx[2], nx2[2];
+  auto load_gate = [&](int i) {
+    const int m = bm + wm * 64 + (lane & 15) + 16 * i;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      nx[h] = nx2[h] = op.bias[h];   // (any defined value: rows past M are not stored)
+      if (m < P.M) {
+        const h16* src = auxz + (long)m * P.ldaux + bn + wn * 64 + 8 * (lane >> 4) + 32 * h;
+        nx[h] = *reinterpret_cast<const h16x8*>(src);
+        nx2[h] = *reinterpret_cast<const h16x8*>(src + P.N);
+      }
+    }
+  };
+  if (GATE_LATE) load_gate(0);
+  char* stage = smem + wid * SLOTB;
+  const int rl = lane & 15, g = lane >> 4;
+  const int m0 = bm + wm * 64 + rl, nw = bn + wn * 64 + 8 * g;
+  h16* C = reinterpret_cast<h16*>(Cz);
+  float bv[2][8];
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bv[h][e] = (float)op.bias[h][e];   // zero without a bias
+  constexpr bool DROPS = EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID;
+  const float dscale = P.thresh ? 1.f / (1.f - P.p) : 1.f;
+  // one mixer per pair of counters while the lane's 2 FR runs share the counter's high word (as the
+  // staged path); a run starts on a multiple of 8 columns, so an even offset and ld_rng keep it even
+  uint32_t hmix = 0, pbase = 0;
+  bool same_hi = false, fast = false;
+  if (DROPS && P.thresh) {
+    const uint64_t cf = P.offset + (uint64_t)m0 * P.ld_rng + nw;
+    const uint64_t cl = P.offset + (uint64_t)(m0 + 16 * (FR - 1)) * P.ld_rng + nw + 39;
+    same_hi = mms_same_hi(cf, cl) && ((cf & 1) == 0) && ((P.ld_rng & 1) == 0);
+    hmix = mms_hi_mix(P.seed, cf);
+    pbase = (uint32_t)(cf >> 1);
+    fast = __all(same_hi);
+  }
+#pragma unroll
+  for (int i = 0; i < FR; ++i) {
+    const int rr = i * 16 + rl, m = m0 + 16 * i;
+    if (GATE_LATE) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) { op.ax[0][h] = nx[h]; op.ax2[0][h] = nx2[h]; }
+      if (i + 1 < FR) load_gate(i + 1);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float x[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = acc[i][2 * h + (e >> 2)][e & 3] * P.alpha + bv[h][e];
+      bool keep[8] = {true, true, true, true, true, true, true, true};
+      if (DROPS && P.thresh && fast) {
+        // pair index of counter offset + (m0 + 16 i) ld_rng + nw + 32 h (ld_rng even)
+        const uint32_t p0 = pbase + (uint32_t)(8 * i) * (uint32_t)P.ld_rng + 16 * h;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const uint32_t hv = mms_mix32((p0 + t) ^ hmix);
+          keep[2 * t] = (hv & 0xffffU) >= P.thresh;
+          keep[2 * t + 1] = (hv >> 16) >= P.thresh;
+        }
+      } else if (DROPS && P.thresh) {
+        const uint64_t c0 = P.offset + (uint64_t)m * P.ld_rng + nw + 32 * h;
+        bool k0[4], k1[4];
+        if (same_hi) {
+          mms_keep4_hi(hmix, c0, P.thresh, k0);
+          mms_keep4_hi(hmix, c0 + 4, P.thresh, k1);
+        } else {
+          mms_keep4(P.seed, c0, P.thresh, k0);
+          mms_keep4(P.seed, c0 + 4, P.thresh, k1);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { keep[e] = k0[e]; keep[e + 4] = k1[e]; }
+      }
+      h16x8 o8;
+      if (EPI == MMS_EPI_GATE) {
+        h16x8 g8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float gt = sigmoidf_(x[e]), ov = (float)op.ax[GATE_LATE ? 0 : i][h][e];
+          const float tv = (float)op.ax2[(EPI == MMS_EPI_GATE && !GATE_LATE) ? i : 0][h][e];
+          g8[e] = (h16)gt;
+          o8[e] = (h16)(tv + gt * (ov - tv));
+        }
+        if (m < P.M) *reinterpret_cast<h16x8*>(P.out2 + (long)m * P.ldo2 + nw + 32 * h) = g8;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float o;
+          if (EPI == MMS_EPI_RELU_DROP) o = keep[e] ? fmaxf(x[e], 0.f) * dscale : 0.f;
+          else if (EPI == MMS_EPI_DROP_RESID) o = (float)op.ax[i][h][e] + (keep[e] ? x[e] * dscale : 0.f);
+          else if (EPI == MMS_EPI_RELU_DROP_BWD) o = (float)op.ax[i][h][e] > 0.f ? x[e] * dscale : 0.f;
+          else if (EPI == MMS_EPI_F16_ACC) o = (float)op.ax[i][h][e] + x[e];
+          else o = x[e];
+          o8[e] = (h16)o;
+        }
+      }
+#if MMS_GEMM_PERM_DIRECT
+      if (m < P.M) *reinterpret_cast<h16x8*>(C + (long)m * P.ldc + nw + 32 * h) = o8;
+#else
+      // 16-B chunk 4 h + g of row rr, XOR-swizzled by rr & 7: a ds_write_b128 group (8 lanes: 8 rows,
+      // one chunk) covers the 32 write banks once; the read-back's lane groups read distinct chunks
+      *reinterpret_cast<h16x8*>(stage + rr * 128 + (((4 * h + g) ^ (rr & 7)) << 4)) = o8;
+#endif
+    }
+  }
+#if !MMS_GEMM_PERM_DIRECT
+  // the slot is re-read by other lanes of this wave: drain its LDS writes first (as reg_epilogue)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  const int q = lane & 7;
+  const int n = bn + wn * 64 + 8 * q;
+#pragma unroll
+  for (int pass = 0; pass < 2 * FR; ++pass) {
+    const int rr = pass * 8 + (lane >> 3);
+    typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
+    const u32x4_ v = *reinterpret_cast<const u32x4_*>(stage + rr * 128 + ((q ^ (rr & 7)) << 4));
+    const int mr = bm + wm * 64 + rr;
+    if (mr < P.M) *reinterpret_cast<u32x4_*>(C + (long)mr * P.ldc + n) = v;
+  }
+#endif
 }
 
 // FR: 16-row fragments of the wave's tile in this pass (4 = 64 rows; 2 = 32 rows); SLOT: floats of
@@ -632,9 +845,12 @@ MMS_DEV h16x8 read_frag32(const char* lds, int sub, int lane) {
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-// one 128-row x 64-k operand stage by LDS-DMA: 16 wave-instructions, wave `wid` issues 4
+// one 128-row x 64-k operand stage by LDS-DMA: 16 wave-instructions, wave `wid` issues 4.
+// perm (K-contiguous weight of a permuted-epilogue launch): LDS row r comes from operand row
+// perm_row(r); the chunk swizzle stays that of the LDS row, which is what the fragment reads undo
 template <bool KC>
-MMS_DEV void dma_tile(__amdgpu_buffer_rsrc_t rs, char* lds, long ld, int row0, int k0rel, int wid, int lane) {
+MMS_DEV void dma_tile(__amdgpu_buffer_rsrc_t rs, char* lds, long ld, int row0, int k0rel, int wid, int lane,
+                      bool perm = false) {
 #ifdef MMS_GEMM_NODMA   // ablation build: no operand traffic (garbage output)
   return;
 #endif
@@ -646,7 +862,7 @@ MMS_DEV void dma_tile(__amdgpu_buffer_rsrc_t rs, char* lds, long ld, int row0, i
     if (KC) {
       const int row = ins * 8 + (lane >> 3), slot = lane & 7;
       const int c = slot ^ (row & 7);
-      voff = (int)(((long)(row0 + row) * ld + k0rel + c * 8) * 2);
+      voff = (int)(((long)(row0 + (perm ? perm_row(row) : row)) * ld + k0rel + c * 8) * 2);
     } else {
       const int kr = ins * 4 + (lane >> 4), slot = lane & 15;
       const int c = slot ^ swz_mn(kr);
