@@ -238,10 +238,7 @@ MMS_DEV void dma_gemm_tile(const GemmP& P, char* smem, int z, int tm, int tn) {
   // issued after a DMA, which would make every k-step wait for the NEXT stage's DMA to land.  With
   // a transpose-read operand the k-step therefore reads both k-halves' fragments first and issues
   // the next stage's DMA behind them (the DMA then overlaps the MFMAs, as in the K-contiguous form).
-#ifndef MMS_GEMM_DMA_AFTER_READS
-#define MMS_GEMM_DMA_AFTER_READS 0
-#endif
-  constexpr bool READ_FIRST = !A_KC || !B_KC || MMS_GEMM_DMA_AFTER_READS;
+  constexpr bool READ_FIRST = !A_KC || !B_KC;
   // All 16 fragments of the stage are read before its MFMAs (the second k-half's reads no longer
   // wait behind the first half's MFMAs): 0-5 % faster isolated on the step's NT shapes, step flat
   // (profiles/round3_v5_gemm_read_all_ab.txt).
@@ -318,9 +315,6 @@ MMS_DEV void dma_gemm_tile(const GemmP& P, char* smem, int z, int tm, int tn) {
   }
   // the ring is idle once every wave is past its last fragment read (no DMA is in flight: the
   // last k-step waited for vmcnt(0))
-#if MMS_GEMM_PERM_DIRECT   // A/B: direct stores use no LDS, so no barrier in front of them
-  if (!perm)
-#endif
   __syncthreads();
 #ifdef MMS_GEMM_NOEPI  // ablation build: no epilogue (accumulators kept live; garbage output)
 #pragma unroll
@@ -401,7 +395,7 @@ __global__ void __launch_bounds__(NT, 2) gemm_tall_kernel(GemmP P, int tiles_m, 
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nk = P.K / BK;   // K % 64 == 0 (host)
   // weight rows permuted for the register epilogue on whole 16-B runs (gemm_common.h perm_epilogue)
-  constexpr bool PERM_T = epi_perm<EPI>() && MMS_GEMM_REG_TALL;
+  constexpr bool PERM_T = epi_perm<EPI>();
   const bool perm = PERM_T && reg_epilogue_ok(P);   // launch-uniform
   constexpr int WR = 16 * FRT, F1 = FRT < 4 ? FRT : 4;
   PermOperands<EPI, FRT> op;
@@ -452,22 +446,12 @@ __global__ void __launch_bounds__(NT, 2) gemm_tall_kernel(GemmP P, int tiles_m, 
   }
 #undef SA
 #undef SB
-#if MMS_GEMM_PERM_DIRECT   // A/B: direct stores use no LDS, so no barrier in front of them
-  if (!perm)
-#endif
   __syncthreads();   // the ring is idle (the last k-step waited for vmcnt(0))
   // the wave's rows [bm + 16 FRT wm, + 16 FRT): fragments 0-3 (64 rows), then the rest, each
   // through the wave's 16 KiB staging area (staged_epilogue places wave rows at bm + 64 wm)
   if constexpr (PERM_T) {   // all FRT fragments in one pass (fp16 slots: 2 KiB per fragment)
     if (perm) {
       perm_epilogue<EPI, FRT, FRT * 2048>(P, smem, acc, op, bm + (WR - 64) * wm, bn, wm, wn, wid, lane, P.C, P.aux);
-      stamp_end(P.stamps, t_start);
-      return;
-    }
-  }
-  if constexpr (epi_regs<EPI>() && MMS_GEMM_REG_TALL) {   // (without MMS_GEMM_PERM) the unpermuted register epilogue
-    if (reg_epilogue_ok(P)) {
-      reg_epilogue<EPI, FRT, FRT * 2048>(P, smem, acc, bm + (WR - 64) * wm, bn, wm, wn, wid, lane, P.C);
       stamp_end(P.stamps, t_start);
       return;
     }
@@ -1258,7 +1242,11 @@ static int* skinny_tickets(hipStream_t stream) {
     }
     int* p = nullptr;
     const size_t bytes = (size_t)kTicketSlices * kTicketCap * sizeof(int);
-    if (hipMalloc(&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess) {
+    // zeroed before any launch can read it: hipMemset alone runs on the null stream and may return
+    // before the fill has executed, and a non-blocking stream's kernels are not ordered behind it (the
+    // first split launch of a process then saw stale tickets now and then and lost its reduction)
+    if (hipMalloc(&p, bytes) != hipSuccess || hipMemsetAsync(p, 0, bytes, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) {
       if (p) (void)hipFree(p);
       mms::set_error("gemm: short-M split tickets: allocation failed");
       return nullptr;
@@ -1302,13 +1290,40 @@ static bool use_256(const mms2ut_gemm_args* a, int nz) {
   return nz == 1 && a->K >= 2048 && a->N >= 1536 && a->M >= 4096;
 }
 
+// The operands a form cannot do without, and GemmP.vec16: every fp16 row operand of the epilogue is
+// 16-B aligned at 8-column granularity (batched: the batch strides of C and aux too; the split-K
+// fixup has batch 1 and ignores them)
+static int epilogue_operands(const mms2ut_gemm_args* a, bool batched, int* vec16) {
+  MMS_REQUIRE(!(a->epi == MMS_EPI_DROP_RESID || a->epi == MMS_EPI_GATE || a->epi == MMS_EPI_GELU_DROP_BWD) || a->aux,
+              "gemm: epilogue needs aux");
+  MMS_REQUIRE(a->epi != MMS_EPI_RELU_DROP_BWD || a->aux, "gemm: RELU_DROP_BWD needs aux");
+  MMS_REQUIRE(!(a->epi == MMS_EPI_GATE || a->epi == MMS_EPI_GELU_DROP) || a->out2, "gemm: epilogue needs out2");
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  bool v = al16(a->C) && a->ldc % 8 == 0 && (!batched || (a->sC1 % 8 == 0 && a->sC2 % 8 == 0));
+  if (a->aux) v = v && al16(a->aux) && a->ldaux % 8 == 0 && (!batched || (a->sX1 % 8 == 0 && a->sX2 % 8 == 0)) &&
+                  (a->epi != MMS_EPI_GATE || a->N % 8 == 0);
+  if (a->out2) v = v && al16(a->out2) && a->ldo2 % 8 == 0;
+  if (a->bias) v = v && al16(a->bias);
+  *vec16 = v ? (g_epi_staged ? 3 : 1) : 0;
+  return 0;
+}
+
+// f(std::bool_constant<A_KC>, std::bool_constant<B_KC>) for the operands' layouts
+template <class F>
+static int by_layout(bool a_kc, bool b_kc, F f) {
+  if (a_kc && b_kc) return f(std::true_type{}, std::true_type{});
+  if (a_kc) return f(std::true_type{}, std::false_type{});
+  if (b_kc) return f(std::false_type{}, std::true_type{});
+  return f(std::false_type{}, std::false_type{});
+}
+
 static int gemm_dispatch(const mms2ut_gemm_args* a, hipStream_t stream) {
   MMS_REQUIRE(a != nullptr, "gemm: null args");
   MMS_REQUIRE(a->M >= 0 && a->N >= 0 && a->K >= 0, "gemm: negative dims");
   if (a->M == 0 || a->N == 0 || a->batch == 0) return 0;
   MMS_REQUIRE(a->lda % 8 == 0 && a->ldb % 8 == 0, "gemm: lda/ldb must be multiples of 8 (lda=%ld ldb=%ld)", a->lda, a->ldb);
   MMS_REQUIRE(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0, "gemm: A/B must be 16-byte aligned");
-  MMS_REQUIRE(a->epi == MMS_EPI_F32 ? (a->ldc % 4 == 0) : (a->ldc % 4 == 0), "gemm: ldc must be a multiple of 4");
+  MMS_REQUIRE(a->ldc % 4 == 0, "gemm: ldc must be a multiple of 4");
   const bool a_kc = a->a_kcontig != 0, b_kc = a->b_kcontig != 0;
   // strides must keep 16-B alignment for every batch
   MMS_REQUIRE(a->sA1 % 8 == 0 && a->sA2 % 8 == 0 && a->sB1 % 8 == 0 && a->sB2 % 8 == 0, "gemm: batch strides must be multiples of 8");
@@ -1348,18 +1363,9 @@ static int gemm_dispatch(const mms2ut_gemm_args* a, hipStream_t stream) {
     F.aux = a->aux; F.ldaux = a->ldaux; F.out2 = a->out2; F.ldo2 = a->ldo2;
     F.p = a->dropout_p; F.thresh = mms_drop_thresh(a->dropout_p); F.seed = a->seed; F.offset = a->offset;
     F.ld_rng = a->ld_rng > 0 ? a->ld_rng : a->N;
-    MMS_REQUIRE(!(a->epi == MMS_EPI_DROP_RESID || a->epi == MMS_EPI_GATE || a->epi == MMS_EPI_GELU_DROP_BWD) || a->aux,
-                "gemm: epilogue needs aux");
-    MMS_REQUIRE(a->epi != MMS_EPI_RELU_DROP_BWD || a->aux, "gemm: RELU_DROP_BWD needs aux");
-    MMS_REQUIRE(!(a->epi == MMS_EPI_GATE || a->epi == MMS_EPI_GELU_DROP) || a->out2, "gemm: epilogue needs out2");
+    if (epilogue_operands(a, false, &F.vec16)) return 1;
     MMS_REQUIRE(a->ldc % 4 == 0 && (!a->aux || (a->ldaux % 4 == 0 && ((uintptr_t)a->aux & 7) == 0)) &&
                 (!a->bias || ((uintptr_t)a->bias & 7) == 0), "gemm: fixup operand alignment");
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    bool v = al16(a->C) && a->ldc % 8 == 0;
-    if (a->aux) v = v && al16(a->aux) && a->ldaux % 8 == 0 && (a->epi != MMS_EPI_GATE || a->N % 8 == 0);
-    if (a->out2) v = v && al16(a->out2) && a->ldo2 % 8 == 0;
-    if (a->bias) v = v && al16(a->bias);
-    F.vec16 = v ? (g_epi_staged ? 3 : 1) : 0;
     F.stamps = stamp_take(((long)a->M * ((a->N + 7) / 8) + 255) / 256);
     return launch_fixup(a->epi, F, a->splitk_ws, splitk, stream);
   }
@@ -1374,19 +1380,7 @@ static int gemm_dispatch(const mms2ut_gemm_args* a, hipStream_t stream) {
   P.p = a->dropout_p; P.thresh = mms_drop_thresh(a->dropout_p); P.seed = a->seed; P.offset = a->offset;
   P.ld_rng = a->ld_rng > 0 ? a->ld_rng : a->N;
   P.group_m = group_m_for((a->M + BM - 1) / BM);
-  MMS_REQUIRE(!(a->epi == MMS_EPI_DROP_RESID || a->epi == MMS_EPI_GATE || a->epi == MMS_EPI_GELU_DROP_BWD) || a->aux,
-              "gemm: epilogue needs aux");
-  MMS_REQUIRE(a->epi != MMS_EPI_RELU_DROP_BWD || a->aux, "gemm: RELU_DROP_BWD needs aux");
-  MMS_REQUIRE(!(a->epi == MMS_EPI_GATE || a->epi == MMS_EPI_GELU_DROP) || a->out2, "gemm: epilogue needs out2");
-  {
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    bool v = al16(a->C) && a->ldc % 8 == 0 && a->sC1 % 8 == 0 && a->sC2 % 8 == 0;
-    if (a->aux) v = v && al16(a->aux) && a->ldaux % 8 == 0 && a->sX1 % 8 == 0 && a->sX2 % 8 == 0 &&
-                    (a->epi != MMS_EPI_GATE || a->N % 8 == 0);
-    if (a->out2) v = v && al16(a->out2) && a->ldo2 % 8 == 0;
-    if (a->bias) v = v && al16(a->bias);
-    P.vec16 = v ? (g_epi_staged ? 3 : 1) : 0;
-  }
+  if (epilogue_operands(a, true, &P.vec16)) return 1;
   if (splitk == 1 && skinny_eligible(a)) {
     const SkinnyPlan pl = skinny_plan(a, a->splitk_ws != nullptr);
     if (pl.code) {
@@ -1435,22 +1429,19 @@ static int gemm_dispatch(const mms2ut_gemm_args* a, hipStream_t stream) {
     if (use_256(a, nz)) {
       const int tm2 = (a->M + BM2 - 1) / BM2, tn2 = (a->N + BN2 - 1) / BN2;
       P.stamps = stamp_take((long)tm2 * tn2 * nz);
-      if (a_kc && b_kc) return launch_256<true, true>(a->epi, P, tm2, tn2, nz, s);
-      if (a_kc && !b_kc) return launch_256<true, false>(a->epi, P, tm2, tn2, nz, s);
-      if (!a_kc && b_kc) return launch_256<false, true>(a->epi, P, tm2, tn2, nz, s);
-      return launch_256<false, false>(a->epi, P, tm2, tn2, nz, s);
+      return by_layout(a_kc, b_kc, [&](auto ak, auto bk) {
+        return launch_256<decltype(ak)::value, decltype(bk)::value>(a->epi, P, tm2, tn2, nz, s);
+      });
     }
     P.stamps = stamp_take((long)tm * tn * nz);
-    if (a_kc && b_kc) return launch_dma<true, true>(a->epi, P, tm, tn, nz, s);
-    if (a_kc && !b_kc) return launch_dma<true, false>(a->epi, P, tm, tn, nz, s);
-    if (!a_kc && b_kc) return launch_dma<false, true>(a->epi, P, tm, tn, nz, s);
-    return launch_dma<false, false>(a->epi, P, tm, tn, nz, s);
+    return by_layout(a_kc, b_kc, [&](auto ak, auto bk) {
+      return launch_dma<decltype(ak)::value, decltype(bk)::value>(a->epi, P, tm, tn, nz, s);
+    });
   }
   P.stamps = stamp_take((long)tm * tn * nz);
-  if (a_kc && b_kc) return launch_epi<true, true>(a->epi, P, tm, tn, nz, s);
-  if (a_kc && !b_kc) return launch_epi<true, false>(a->epi, P, tm, tn, nz, s);
-  if (!a_kc && b_kc) return launch_epi<false, true>(a->epi, P, tm, tn, nz, s);
-  return launch_epi<false, false>(a->epi, P, tm, tn, nz, s);
+  return by_layout(a_kc, b_kc, [&](auto ak, auto bk) {
+    return launch_epi<decltype(ak)::value, decltype(bk)::value>(a->epi, P, tm, tn, nz, s);
+  });
 }
 
 namespace mms {

@@ -93,6 +93,102 @@ MMS_DEV float gelu_grad_(float z) {
   return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.39894228040143268f * __expf(-0.5f * z * z);
 }
 
+// ------------------------------------------------------------------------------------------
+// What each epilogue form needs.  MMS_EPI_F32 (the split-K / weight-gradient slab) is alpha * acc
+// and nothing else.
+// ------------------------------------------------------------------------------------------
+template <int EPI>
+constexpr bool epi_drops() {
+  return EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GELU_DROP ||
+         EPI == MMS_EPI_GELU_DROP_BWD;
+}
+// adds P.bias (when set): every fp16 form but the two that scale an incoming gradient
+template <int EPI>
+constexpr bool epi_adds_bias() {
+  return EPI != MMS_EPI_F32 && EPI != MMS_EPI_RELU_DROP_BWD && EPI != MMS_EPI_GELU_DROP_BWD;
+}
+// reads a row operand at the element's (m, n): aux (residual: DROP_RESID; o: GATE; fc1 output:
+// RELU_DROP_BWD; pre-activation z: GELU_DROP_BWD) or the old C (F16_ACC).  GATE reads a second
+// operand, t, at aux + N of the same row.
+template <int EPI>
+constexpr bool epi_reads_row() {
+  return EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GATE || EPI == MMS_EPI_RELU_DROP_BWD ||
+         EPI == MMS_EPI_F16_ACC || EPI == MMS_EPI_GELU_DROP_BWD;
+}
+// writes P.out2: the gate (GATE), the fp16 pre-activation z (GELU_DROP)
+template <int EPI>
+constexpr bool epi_writes_out2() { return EPI == MMS_EPI_GATE || EPI == MMS_EPI_GELU_DROP; }
+
+// One element of an fp16 form: x = acc * alpha + bias, a the row operand (aux / old C), a2 GATE's
+// second operand (aux + N), keep the element's dropout bit, dscale = 1 / (1 - p) (1 without dropout).
+// Returns the fp32 value that the caller rounds to fp16 and sets o2 to the out2 value of the forms
+// that write one.  reg_epilogue, perm_epilogue and the staged fast path call this, so the fp32 ->
+// fp16 rounding points (GELU_DROP applies gelu to the ROUNDED z) are the same on all of them.
+// epilogue_store / epilogue_store8 below still spell the same expressions out form by form: hipcc
+// fuses a form's last multiply with the fp16 rounding (v_fma_mixlo_f16: one rounding instead of two)
+// or not depending on how those loops vectorise, and written through this function they fused
+// where the former code did not (ReLU-dropout and gate outputs differed in rare last bits).
+template <int EPI>
+MMS_DEV float epi_element(float x, float a, float a2, bool keep, float dscale, h16& o2) {
+  if (EPI == MMS_EPI_RELU_DROP) return keep ? fmaxf(x, 0.f) * dscale : 0.f;
+  if (EPI == MMS_EPI_DROP_RESID) return a + (keep ? x * dscale : 0.f);
+  if (EPI == MMS_EPI_GATE) {   // a = o, a2 = t
+    const float g = sigmoidf_(x);
+    o2 = (h16)g;
+    return a2 + g * (a - a2);
+  }
+  if (EPI == MMS_EPI_RELU_DROP_BWD) return a > 0.f ? x * dscale : 0.f;   // (the mask is folded into a)
+  if (EPI == MMS_EPI_F16_ACC) return a + x;
+  if (EPI == MMS_EPI_GELU_DROP) {
+    o2 = (h16)x;
+    return keep ? gelu_((float)o2) * dscale : 0.f;
+  }
+  if (EPI == MMS_EPI_GELU_DROP_BWD) return keep ? x * dscale * gelu_grad_(a) : 0.f;
+  return x;
+}
+
+// Keep bits of a lane's runs of W (4 / 8) consecutive dropout counters.  init() takes the first and
+// the last counter the lane will ask for: while they share the counter's high word (always, unless
+// the lane's elements straddle a 2^33 boundary) the seed / high-word half of the hash is one
+// constant, one mixer per pair of elements instead of two; when that holds for the whole wave
+// (the compiler versions the caller's loop on it) a run's pair index is pbase + dpair in 32-bit
+// arithmetic, no 64-bit counter per run.  A run starts on a multiple of 4 columns, so an even
+// offset and ld_rng keep its first counter even.  Bit-identical to mms_keep4 on every tier
+// (tests/test_rng_ref.py).
+template <int W>
+struct KeepRuns {
+  uint32_t hmix = 0, pbase = 0;
+  bool same_hi = false, fast = false;
+  MMS_DEV void init(const GemmP& P, uint64_t cf, uint64_t cl) {
+    same_hi = mms_same_hi(cf, cl) && ((cf & 1) == 0) && ((P.ld_rng & 1) == 0);
+    hmix = mms_hi_mix(P.seed, cf);
+    pbase = (uint32_t)(cf >> 1);
+    fast = __all(same_hi);
+  }
+  // the run at (m, n): counters offset + m ld_rng + n .. + W - 1; dpair = its pair index less cf's
+  MMS_DEV void run(const GemmP& P, uint32_t dpair, int m, int n, bool (&keep)[W]) const {
+    if (fast) {
+      const uint32_t p0 = pbase + dpair;
+#pragma unroll
+      for (int t = 0; t < W / 2; ++t) {
+        const uint32_t hv = mms_mix32((p0 + t) ^ hmix);
+        keep[2 * t] = (hv & 0xffffU) >= P.thresh;
+        keep[2 * t + 1] = (hv >> 16) >= P.thresh;
+      }
+    } else {
+      const uint64_t c0 = P.offset + (uint64_t)m * P.ld_rng + n;
+#pragma unroll
+      for (int t = 0; t < W / 4; ++t) {
+        bool k[4];
+        if (same_hi) mms_keep4_hi(hmix, c0 + 4 * t, P.thresh, k);
+        else mms_keep4(P.seed, c0 + 4 * t, P.thresh, k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) keep[4 * t + e] = k[e];
+      }
+    }
+  }
+};
+
 template <int EPI>
 MMS_DEV void epilogue_store(const GemmP& P, void* Cz, const h16* auxz, int m, int n, f32x4 v) {
   if (m >= P.M) return;
@@ -108,7 +204,7 @@ MMS_DEV void epilogue_store(const GemmP& P, void* Cz, const h16* auxz, int m, in
     return;
   }
   const bool full = n + 3 < N;
-  if (P.bias && EPI != MMS_EPI_RELU_DROP_BWD && EPI != MMS_EPI_GELU_DROP_BWD) {
+  if (epi_adds_bias<EPI>() && P.bias) {
     if (full) {
       const h16x4 bv = *reinterpret_cast<const h16x4*>(P.bias + n);
 #pragma unroll
@@ -131,8 +227,7 @@ MMS_DEV void epilogue_store(const GemmP& P, void* Cz, const h16* auxz, int m, in
     }
   };
   bool keep[4] = {true, true, true, true};
-  if ((EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GELU_DROP ||
-       EPI == MMS_EPI_GELU_DROP_BWD) && P.thresh)
+  if (epi_drops<EPI>() && P.thresh)
     mms_keep4(P.seed, P.offset + (uint64_t)m * P.ld_rng + n, P.thresh, keep);
   const float dscale = P.thresh ? 1.f / (1.f - P.p) : 1.f;
   float o[4];
@@ -223,7 +318,7 @@ MMS_DEV void epilogue_store8(const GemmP& P, void* Cz, const h16* auxz, int m, i
   float x[8];
 #pragma unroll
   for (int r = 0; r < 8; ++r) x[r] = v[r] * P.alpha;
-  if (P.bias && EPI != MMS_EPI_RELU_DROP_BWD && EPI != MMS_EPI_GELU_DROP_BWD) {
+  if (epi_adds_bias<EPI>() && P.bias) {
     const h16x8 bv = *reinterpret_cast<const h16x8*>(P.bias + n);
 #pragma unroll
     for (int r = 0; r < 8; ++r) x[r] += (float)bv[r];
@@ -235,8 +330,7 @@ MMS_DEV void epilogue_store8(const GemmP& P, void* Cz, const h16* auxz, int m, i
     for (int r = 0; r < 8; ++r) o[r] = (float)t[r];
   };
   bool keep[8] = {true, true, true, true, true, true, true, true};
-  if ((EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GELU_DROP ||
-       EPI == MMS_EPI_GELU_DROP_BWD) && P.thresh) {
+  if (epi_drops<EPI>() && P.thresh) {
     const uint64_t c0 = P.offset + (uint64_t)m * P.ld_rng + n;
     bool k0[4], k1[4];
     mms_keep4(P.seed, c0, P.thresh, k0);
@@ -300,10 +394,6 @@ MMS_DEV void epilogue_store8(const GemmP& P, void* Cz, const h16* auxz, int m, i
   *reinterpret_cast<h16x8*>(C + n) = ov8;
 }
 
-// Epilogue through LDS: each wave parks its 64x64 fp32 accumulator tile in 16 KiB of the (now idle)
-// operand ring, XOR-swizzled by row, then re-reads it row-major so a lane owns 8 consecutive
-// columns: every global load/store of the epilogue covers whole 128-B row segments instead of
-// 16 rows x 32 B.  Caller guarantees all waves are past their last operand read.
 // Block -> (z, tm, tn).  The grid is 1-D over tiles_m * tiles_n * nz.  Workgroups are dispatched
 // round-robin over the 8 XCDs, each with a private 4 MiB L2, so the linear id is first remapped
 // (bijectively) to give every XCD one contiguous range of the z-major tile space: a split-K
@@ -324,12 +414,6 @@ MMS_DEV void tile_coords(int bid, int tiles_m, int tiles_n, int total, int& z, i
   tn = w / gsize;
 }
 
-template <int EPI>
-constexpr bool epi_drops() {
-  return EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GELU_DROP ||
-         EPI == MMS_EPI_GELU_DROP_BWD;
-}
-
 // Register epilogue (round 6): for the epilogues whose element math needs no operand in row-major
 // order (plain / bias, ReLU-dropout) the math runs on the accumulators in the MFMA layout (lane l:
 // row 16 i + (l & 15), columns 16 j + 4 (l >> 4) .. + 3), the fp16 results go through the wave's own
@@ -339,19 +423,8 @@ constexpr bool epi_drops() {
 // one wave only, so no workgroup barrier sits between the two.  The NT LDS-DMA kernels use the
 // permuted form below (perm_epilogue), which also carries the operand-reading epilogues; this one
 // serves the kernels whose weight rows are not permuted (register-staged, 256x256, TN / NN, grouped).
-#ifndef MMS_GEMM_REG_EPI
-#define MMS_GEMM_REG_EPI 1
-#endif
-#ifndef MMS_GEMM_REG_STAGED
-#define MMS_GEMM_REG_STAGED 1
-#endif
-#ifndef MMS_GEMM_REG_TALL
-#define MMS_GEMM_REG_TALL 1
-#endif
 template <int EPI>
-constexpr bool epi_regs() {
-  return MMS_GEMM_REG_EPI && (EPI == MMS_EPI_F16 || EPI == MMS_EPI_RELU_DROP);
-}
+constexpr bool epi_regs() { return EPI == MMS_EPI_F16 || EPI == MMS_EPI_RELU_DROP; }
 
 // The choice between this and the staged path must be the same for every wave of a block: the two
 // lay their LDS slots out differently (the tall kernel packs the fp16 slots) and the staged path
@@ -374,7 +447,7 @@ MMS_DEV void reg_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4],
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) bv[j][e] = 0.f;
-  if (P.bias) {
+  if (epi_adds_bias<EPI>() && P.bias) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const h16x4 b4 = *reinterpret_cast<const h16x4*>(P.bias + nw + 16 * j);
@@ -382,45 +455,26 @@ MMS_DEV void reg_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4],
       for (int e = 0; e < 4; ++e) bv[j][e] = (float)b4[e];
     }
   }
-  constexpr bool DROPS = EPI == MMS_EPI_RELU_DROP;
+  constexpr bool DROPS = epi_drops<EPI>();
   const float dscale = P.thresh ? 1.f / (1.f - P.p) : 1.f;
-  uint32_t hmix = 0, pbase = 0;
-  bool fast = false;
-  if (DROPS && P.thresh) {
-    const uint64_t cf = P.offset + (uint64_t)m0 * P.ld_rng + nw;
-    const uint64_t cl = P.offset + (uint64_t)(m0 + 16 * (FR - 1)) * P.ld_rng + nw + 51;
-    const bool sh = mms_same_hi(cf, cl) && ((cf & 1) == 0) && ((P.ld_rng & 1) == 0);
-    hmix = mms_hi_mix(P.seed, cf);
-    pbase = (uint32_t)(cf >> 1);
-    fast = __all(sh);
-  }
+  // the lane's 4 FR runs: rows m0 + 16 i, columns nw + 16 j .. + 3
+  KeepRuns<4> kr;
+  if (DROPS && P.thresh)
+    kr.init(P, P.offset + (uint64_t)m0 * P.ld_rng + nw,
+            P.offset + (uint64_t)(m0 + 16 * (FR - 1)) * P.ld_rng + nw + 51);
 #pragma unroll
   for (int i = 0; i < FR; ++i) {
     const int rr = i * 16 + rl;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float x[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) x[e] = acc[i][j][e] * P.alpha + bv[j][e];
       bool keep[4] = {true, true, true, true};
-      if (DROPS && P.thresh && fast) {
-        // pair index of counter offset + (m0 + 16 i) ld_rng + nw + 16 j (ld_rng even)
-        const uint32_t p0 = pbase + (uint32_t)(8 * i) * (uint32_t)P.ld_rng + 8 * j;
-        const uint32_t h0 = mms_mix32(p0 ^ hmix), h1 = mms_mix32((p0 + 1) ^ hmix);
-        keep[0] = (h0 & 0xffffU) >= P.thresh;
-        keep[1] = (h0 >> 16) >= P.thresh;
-        keep[2] = (h1 & 0xffffU) >= P.thresh;
-        keep[3] = (h1 >> 16) >= P.thresh;
-      } else if (DROPS && P.thresh) {
-        mms_keep4(P.seed, P.offset + (uint64_t)(m0 + 16 * i) * P.ld_rng + nw + 16 * j, P.thresh, keep);
-      }
+      if (DROPS && P.thresh)   // (dpair: 16 i rows and 16 j columns on, in pairs; ld_rng even on that path)
+        kr.run(P, (uint32_t)(8 * i) * (uint32_t)P.ld_rng + 8 * j, m0 + 16 * i, nw + 16 * j, keep);
       h16x4 o4;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float o;
-        if (EPI == MMS_EPI_RELU_DROP) o = keep[e] ? fmaxf(x[e], 0.f) * dscale : 0.f;
-        else o = x[e];
-        o4[e] = (h16)o;
+        h16 o2 = (h16)0.f;   // (no form served here writes out2)
+        o4[e] = (h16)epi_element<EPI>(acc[i][j][e] * P.alpha + bv[j][e], 0.f, 0.f, keep[e], dscale, o2);
       }
       // 16-B chunk 2 j + (g >> 1) of row rr, 8-B half g & 1; chunks XOR-swizzled by (rr >> 1) & 7 and
       // halves by rr & 1: a ds_write_b64 16-lane group (16 rows, one (j, g)) covers the 32 write banks
@@ -459,19 +513,13 @@ MMS_DEV void reg_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4],
 // and a barrier — and the element math runs on the accumulators.  Same expressions, fp32 -> fp16
 // rounding points and dropout counters (offset + m ld_rng + n of the element's true (m, n)) as the
 // staged path: bit-identical.  Launch-uniform choice (reg_epilogue_ok), as for reg_epilogue.
-#ifndef MMS_GEMM_PERM
-#define MMS_GEMM_PERM 1
-#endif
-// A/B: the two 16-B runs of a lane stored straight from the MFMA layout (16 rows x 64 B per
-// instruction, no LDS) instead of through the wave's fp16 slot (whole 128-B row segments)
-#ifndef MMS_GEMM_PERM_DIRECT
-#define MMS_GEMM_PERM_DIRECT 0
-#endif
+// The results go out through the wave's fp16 slot (whole 128-B row segments); storing a lane's two
+// 16-B runs straight from the MFMA layout (16 rows x 64 B per instruction, no LDS) measured level
+// and is not in the tree.
 template <int EPI>
 constexpr bool epi_perm() {
-  return MMS_GEMM_REG_EPI && MMS_GEMM_PERM &&
-         (EPI == MMS_EPI_F16 || EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GATE ||
-          EPI == MMS_EPI_RELU_DROP_BWD || EPI == MMS_EPI_F16_ACC);
+  return EPI == MMS_EPI_F16 || EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GATE ||
+         EPI == MMS_EPI_RELU_DROP_BWD || EPI == MMS_EPI_F16_ACC;
 }
 MMS_DEV int perm_row(int r) { return (r & ~0x1c) | ((r & 0x0c) << 1) | ((r & 0x10) >> 2); }
 
@@ -497,8 +545,7 @@ MMS_DEV void perm_prefetch(const GemmP& P, PermOperands<EPI, FR>& op, int bm, in
   h16x8 z8;
 #pragma unroll
   for (int e = 0; e < 8; ++e) z8[e] = (h16)0.f;
-  constexpr bool LOADS = (EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GATE || EPI == MMS_EPI_RELU_DROP_BWD ||
-                          EPI == MMS_EPI_F16_ACC) && !perm_gate_late<EPI, FR>();
+  constexpr bool LOADS = epi_reads_row<EPI>() && !perm_gate_late<EPI, FR>();
   op.bias[0] = op.bias[1] = z8;
 #pragma unroll
   for (int i = 0; i < FR; ++i) op.ax[i][0] = op.ax[i][1] = z8;
@@ -506,7 +553,7 @@ MMS_DEV void perm_prefetch(const GemmP& P, PermOperands<EPI, FR>& op, int bm, in
   for (int i = 0; i < (EPI == MMS_EPI_GATE ? FR : 1); ++i) op.ax2[i][0] = op.ax2[i][1] = z8;
   if (bn + wn * 64 >= P.N) return;   // wave-uniform
   const int m0 = bm + wm * 64 + (lane & 15), nw = bn + wn * 64 + 8 * (lane >> 4);
-  if (EPI != MMS_EPI_RELU_DROP_BWD && P.bias) {
+  if (epi_adds_bias<EPI>() && P.bias) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) op.bias[h] = *reinterpret_cast<const h16x8*>(P.bias + nw + 32 * h);
   }
@@ -560,20 +607,13 @@ MMS_DEV void perm_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4]
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int e = 0; e < 8; ++e) bv[h][e] = (float)op.bias[h][e];   // zero without a bias
-  constexpr bool DROPS = EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID;
+  constexpr bool DROPS = epi_drops<EPI>();
   const float dscale = P.thresh ? 1.f / (1.f - P.p) : 1.f;
-  // one mixer per pair of counters while the lane's 2 FR runs share the counter's high word (as the
-  // staged path); a run starts on a multiple of 8 columns, so an even offset and ld_rng keep it even
-  uint32_t hmix = 0, pbase = 0;
-  bool same_hi = false, fast = false;
-  if (DROPS && P.thresh) {
-    const uint64_t cf = P.offset + (uint64_t)m0 * P.ld_rng + nw;
-    const uint64_t cl = P.offset + (uint64_t)(m0 + 16 * (FR - 1)) * P.ld_rng + nw + 39;
-    same_hi = mms_same_hi(cf, cl) && ((cf & 1) == 0) && ((P.ld_rng & 1) == 0);
-    hmix = mms_hi_mix(P.seed, cf);
-    pbase = (uint32_t)(cf >> 1);
-    fast = __all(same_hi);
-  }
+  // the lane's 2 FR runs: rows m0 + 16 i, columns nw + 32 h .. + 7
+  KeepRuns<8> kr;
+  if (DROPS && P.thresh)
+    kr.init(P, P.offset + (uint64_t)m0 * P.ld_rng + nw,
+            P.offset + (uint64_t)(m0 + 16 * (FR - 1)) * P.ld_rng + nw + 39);
 #pragma unroll
   for (int i = 0; i < FR; ++i) {
     const int rr = i * 16 + rl, m = m0 + 16 * i;
@@ -588,61 +628,23 @@ MMS_DEV void perm_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4]
 #pragma unroll
       for (int e = 0; e < 8; ++e) x[e] = acc[i][2 * h + (e >> 2)][e & 3] * P.alpha + bv[h][e];
       bool keep[8] = {true, true, true, true, true, true, true, true};
-      if (DROPS && P.thresh && fast) {
-        // pair index of counter offset + (m0 + 16 i) ld_rng + nw + 32 h (ld_rng even)
-        const uint32_t p0 = pbase + (uint32_t)(8 * i) * (uint32_t)P.ld_rng + 16 * h;
+      if (DROPS && P.thresh)   // (dpair: 16 i rows and 32 h columns on, in pairs; ld_rng even on that path)
+        kr.run(P, (uint32_t)(8 * i) * (uint32_t)P.ld_rng + 16 * h, m, nw + 32 * h, keep);
+      const h16x8& a8 = op.ax[GATE_LATE ? 0 : i][h];
+      const h16x8& t8 = op.ax2[(EPI == MMS_EPI_GATE && !GATE_LATE) ? i : 0][h];   // GATE only
+      h16x8 o8, p8;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const uint32_t hv = mms_mix32((p0 + t) ^ hmix);
-          keep[2 * t] = (hv & 0xffffU) >= P.thresh;
-          keep[2 * t + 1] = (hv >> 16) >= P.thresh;
-        }
-      } else if (DROPS && P.thresh) {
-        const uint64_t c0 = P.offset + (uint64_t)m * P.ld_rng + nw + 32 * h;
-        bool k0[4], k1[4];
-        if (same_hi) {
-          mms_keep4_hi(hmix, c0, P.thresh, k0);
-          mms_keep4_hi(hmix, c0 + 4, P.thresh, k1);
-        } else {
-          mms_keep4(P.seed, c0, P.thresh, k0);
-          mms_keep4(P.seed, c0 + 4, P.thresh, k1);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { keep[e] = k0[e]; keep[e + 4] = k1[e]; }
+      for (int e = 0; e < 8; ++e) {
+        h16 o2 = (h16)0.f;
+        o8[e] = (h16)epi_element<EPI>(x[e], (float)a8[e], (float)t8[e], keep[e], dscale, o2);
+        p8[e] = o2;
       }
-      h16x8 o8;
-      if (EPI == MMS_EPI_GATE) {
-        h16x8 g8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float gt = sigmoidf_(x[e]), ov = (float)op.ax[GATE_LATE ? 0 : i][h][e];
-          const float tv = (float)op.ax2[(EPI == MMS_EPI_GATE && !GATE_LATE) ? i : 0][h][e];
-          g8[e] = (h16)gt;
-          o8[e] = (h16)(tv + gt * (ov - tv));
-        }
-        if (m < P.M) *reinterpret_cast<h16x8*>(P.out2 + (long)m * P.ldo2 + nw + 32 * h) = g8;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float o;
-          if (EPI == MMS_EPI_RELU_DROP) o = keep[e] ? fmaxf(x[e], 0.f) * dscale : 0.f;
-          else if (EPI == MMS_EPI_DROP_RESID) o = (float)op.ax[i][h][e] + (keep[e] ? x[e] * dscale : 0.f);
-          else if (EPI == MMS_EPI_RELU_DROP_BWD) o = (float)op.ax[i][h][e] > 0.f ? x[e] * dscale : 0.f;
-          else if (EPI == MMS_EPI_F16_ACC) o = (float)op.ax[i][h][e] + x[e];
-          else o = x[e];
-          o8[e] = (h16)o;
-        }
-      }
-#if MMS_GEMM_PERM_DIRECT
-      if (m < P.M) *reinterpret_cast<h16x8*>(C + (long)m * P.ldc + nw + 32 * h) = o8;
-#else
+      if (epi_writes_out2<EPI>() && m < P.M) *reinterpret_cast<h16x8*>(P.out2 + (long)m * P.ldo2 + nw + 32 * h) = p8;
       // 16-B chunk 4 h + g of row rr, XOR-swizzled by rr & 7: a ds_write_b128 group (8 lanes: 8 rows,
       // one chunk) covers the 32 write banks once; the read-back's lane groups read distinct chunks
       *reinterpret_cast<h16x8*>(stage + rr * 128 + (((4 * h + g) ^ (rr & 7)) << 4)) = o8;
-#endif
     }
   }
-#if !MMS_GEMM_PERM_DIRECT
   // the slot is re-read by other lanes of this wave: drain its LDS writes first (as reg_epilogue)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
@@ -656,16 +658,19 @@ MMS_DEV void perm_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4]
     const int mr = bm + wm * 64 + rr;
     if (mr < P.M) *reinterpret_cast<u32x4_*>(C + (long)mr * P.ldc + n) = v;
   }
-#endif
 }
 
+// Epilogue through LDS: each wave parks its 64x64 fp32 accumulator tile in 16 KiB of the (now idle)
+// operand ring, XOR-swizzled by row, then re-reads it row-major so a lane owns 8 consecutive
+// columns: every global load/store of the epilogue covers whole 128-B row segments instead of
+// 16 rows x 32 B.  Caller guarantees all waves are past their last operand read.
 // FR: 16-row fragments of the wave's tile in this pass (4 = 64 rows; 2 = 32 rows); SLOT: floats of
 // LDS between consecutive waves' staging areas (>= FR * 16 * 64)
 template <int EPI, int FR = 4, int SLOT = 64 * 64>
 MMS_DEV void staged_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][4], int bm, int bn,
                              int wm, int wn, int wid, int lane, void* Cz, const h16* auxz) {
   static_assert(SLOT >= FR * 16 * 64, "staging slot too small");
-  if constexpr (epi_regs<EPI>() && MMS_GEMM_REG_STAGED) {
+  if constexpr (epi_regs<EPI>()) {
     if (reg_epilogue_ok(P)) {   // launch-uniform: every wave of the block takes the same path
       reg_epilogue<EPI, FR, SLOT * 4>(P, smem, acc, bm, bn, wm, wn, wid, lane, Cz);
       return;
@@ -690,8 +695,6 @@ MMS_DEV void staged_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][
     v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
     v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
   };
-  constexpr bool LOADS = EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GATE || EPI == MMS_EPI_RELU_DROP_BWD ||
-                         EPI == MMS_EPI_F16_ACC || EPI == MMS_EPI_GELU_DROP_BWD;
   if (EPI == MMS_EPI_F32 || !(P.vec16 && n + 7 < P.N)) {
 #pragma unroll 2
     for (int pass = 0; pass < PASSES; ++pass) {
@@ -708,7 +711,7 @@ MMS_DEV void staged_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][
   // serialised the epilogue into 8 dependent global round trips.
   const int m0 = bm + wm * 64 + (lane >> 3);
   float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (EPI != MMS_EPI_RELU_DROP_BWD && EPI != MMS_EPI_GELU_DROP_BWD && P.bias) {
+  if (epi_adds_bias<EPI>() && P.bias) {
     const h16x8 b8 = *reinterpret_cast<const h16x8*>(P.bias + n);
 #pragma unroll
     for (int e = 0; e < 8; ++e) bv[e] = (float)b8[e];
@@ -721,7 +724,7 @@ MMS_DEV void staged_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][
     const int m = m0 + 8 * pass;
     ax[pass] = z8;
     ax2[pass] = z8;
-    if (LOADS && m < P.M) {
+    if (epi_reads_row<EPI>() && m < P.M) {
       if (EPI == MMS_EPI_F16_ACC) {
         ax[pass] = *reinterpret_cast<const h16x8*>(C + (long)m * P.ldc + n);
       } else {
@@ -731,23 +734,12 @@ MMS_DEV void staged_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][
     }
   }
   const float dscale = P.thresh ? 1.f / (1.f - P.p) : 1.f;
-  constexpr bool DROPS = EPI == MMS_EPI_RELU_DROP || EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_GELU_DROP ||
-                         EPI == MMS_EPI_GELU_DROP_BWD;
-  // the seed / high-counter half of the dropout hash is one constant for all 64 of this lane's
-  // counters whenever they share the high word (always, unless the run straddles a 2^33
-  // boundary): one mixer per pair of elements instead of two (bit-identical to mms_keep4)
-  uint32_t hmix = 0, pbase = 0;
-  bool same_hi = false, fast = false;
-  if (DROPS && P.thresh) {
-    const uint64_t cf = P.offset + (uint64_t)m0 * P.ld_rng + n;
-    const uint64_t cl = P.offset + (uint64_t)(m0 + 8 * (PASSES - 1)) * P.ld_rng + n + 7;
-    same_hi = mms_same_hi(cf, cl) && ((cf & 1) == 0) && ((P.ld_rng & 1) == 0);
-    hmix = mms_hi_mix(P.seed, cf);
-    // wave-uniform fast path (the compiler versions the pass loop on it): pass p's first pair index
-    // is pbase + 4 p ld_rng, in 32-bit arithmetic, no 64-bit counter per pass
-    pbase = (uint32_t)(cf >> 1);
-    fast = __all(same_hi);
-  }
+  constexpr bool DROPS = epi_drops<EPI>();
+  // the lane's PASSES runs: rows m0 + 8 pass, columns n .. n + 7
+  KeepRuns<8> kr;
+  if (DROPS && P.thresh)
+    kr.init(P, P.offset + (uint64_t)m0 * P.ld_rng + n,
+            P.offset + (uint64_t)(m0 + 8 * (PASSES - 1)) * P.ld_rng + n + 7);
 #pragma unroll
   for (int pass = 0; pass < PASSES; ++pass) {
     const int m = m0 + 8 * pass;
@@ -757,65 +749,18 @@ MMS_DEV void staged_epilogue(const GemmP& P, char* smem, const f32x4 (&acc)[FR][
 #pragma unroll
     for (int e = 0; e < 8; ++e) x[e] = x[e] * P.alpha + bv[e];
     bool keep[8] = {true, true, true, true, true, true, true, true};
-    if (DROPS && P.thresh && fast) {
-      const uint32_t p0 = pbase + (uint32_t)(4 * pass) * (uint32_t)P.ld_rng;
+    if (DROPS && P.thresh)   // (dpair: 8 pass rows on, in pairs; ld_rng even on that path)
+      kr.run(P, (uint32_t)(4 * pass) * (uint32_t)P.ld_rng, m, n, keep);
+    h16x8 o8, p8;
 #pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        const uint32_t hv = mms_mix32((p0 + h) ^ hmix);
-        keep[2 * h] = (hv & 0xffffU) >= P.thresh;
-        keep[2 * h + 1] = (hv >> 16) >= P.thresh;
-      }
-    } else if (DROPS && P.thresh) {
-      const uint64_t c0 = P.offset + (uint64_t)m * P.ld_rng + n;
-      bool k0[4], k1[4];
-      if (same_hi) {
-        mms_keep4_hi(hmix, c0, P.thresh, k0);
-        mms_keep4_hi(hmix, c0 + 4, P.thresh, k1);
-      } else {
-        mms_keep4(P.seed, c0, P.thresh, k0);
-        mms_keep4(P.seed, c0 + 4, P.thresh, k1);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { keep[e] = k0[e]; keep[e + 4] = k1[e]; }
+    for (int e = 0; e < 8; ++e) {
+      h16 o2 = (h16)0.f;
+      o8[e] = (h16)epi_element<EPI>(x[e], (float)ax[pass][e], (float)ax2[pass][e], keep[e], dscale, o2);
+      p8[e] = o2;
     }
-    h16x8 o8;
-    if (EPI == MMS_EPI_GATE) {
-      h16x8 g8;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float g = sigmoidf_(x[e]), ov = (float)ax[pass][e], tv = (float)ax2[pass][e];
-        g8[e] = (h16)g;
-        o8[e] = (h16)(tv + g * (ov - tv));
-      }
-      *reinterpret_cast<h16x8*>(P.out2 + (long)m * P.ldo2 + n) = g8;
-    } else if (EPI == MMS_EPI_GELU_DROP) {
-      h16x8 z8;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        z8[e] = (h16)x[e];
-        o8[e] = (h16)(keep[e] ? gelu_((float)z8[e]) * dscale : 0.f);
-      }
-      *reinterpret_cast<h16x8*>(P.out2 + (long)m * P.ldo2 + n) = z8;
-    } else if (EPI == MMS_EPI_GELU_DROP_BWD) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        o8[e] = (h16)(keep[e] ? x[e] * dscale * gelu_grad_((float)ax[pass][e]) : 0.f);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float o;
-        if (EPI == MMS_EPI_RELU_DROP) o = keep[e] ? fmaxf(x[e], 0.f) * dscale : 0.f;
-        else if (EPI == MMS_EPI_DROP_RESID) o = (float)ax[pass][e] + (keep[e] ? x[e] * dscale : 0.f);
-        else if (EPI == MMS_EPI_RELU_DROP_BWD) o = (float)ax[pass][e] > 0.f ? x[e] * dscale : 0.f;
-        else if (EPI == MMS_EPI_F16_ACC) o = (float)ax[pass][e] + x[e];
-        else o = x[e];
-        o8[e] = (h16)o;
-      }
-    }
+    if (epi_writes_out2<EPI>()) *reinterpret_cast<h16x8*>(P.out2 + (long)m * P.ldo2 + n) = p8;
 #if defined(MMS_LAB_NOSTORE)   // lab ablation build (scripts/micro): the epilogue without its C stores
     asm volatile("" ::"v"(o8));
-#elif defined(MMS_GEMM_NT_STORE)
-    __builtin_nontemporal_store(o8, reinterpret_cast<h16x8*>(C + (long)m * P.ldc + n));
 #else
     *reinterpret_cast<h16x8*>(C + (long)m * P.ldc + n) = o8;
 #endif

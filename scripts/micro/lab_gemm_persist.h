@@ -35,41 +35,18 @@ constexpr bool pt_aux() {
   return EPI == MMS_EPI_DROP_RESID || EPI == MMS_EPI_RELU_DROP_BWD;
 }
 
-// tile-uniform dropout state: the fast path (every counter of the tile shares its pair index's high
-// word; even offset and row stride) mixes one 32-bit word per element pair
-struct PtDrop {
-  bool fast;
-  uint32_t hmix, pbase;
-};
-
-// staged_epilogue's arithmetic on one fragment (lane's 4 columns n0..n0+3 of row m) -> 4 fp16
+// staged_epilogue's arithmetic on one fragment (lane's 4 columns n0..n0+3 of row m) -> 4 fp16;
+// dpair: the run's pair index less that of the lane's first counter (KeepRuns)
 template <int EPI>
-MMS_DEV pu32x2 pt_frag(const GemmP& P, const f32x4& v, const float (&bv)[4], const h16x4& ax, const PtDrop& D,
-                       uint32_t pair0, int m, int n0, float dscale) {
-  float x[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) x[e] = v[e] * P.alpha + bv[e];
+MMS_DEV pu32x2 pt_frag(const GemmP& P, const f32x4& v, const float (&bv)[4], const h16x4& ax, const KeepRuns<4>& kr,
+                       uint32_t dpair, int m, int n0, float dscale) {
   bool keep[4] = {true, true, true, true};
-  if (epi_drops<EPI>() && P.thresh) {
-    if (D.fast) {
-      const uint32_t h0 = mms_mix32(pair0 ^ D.hmix), h1 = mms_mix32((pair0 + 1) ^ D.hmix);
-      keep[0] = (h0 & 0xffffU) >= P.thresh;
-      keep[1] = (h0 >> 16) >= P.thresh;
-      keep[2] = (h1 & 0xffffU) >= P.thresh;
-      keep[3] = (h1 >> 16) >= P.thresh;
-    } else {
-      mms_keep4(P.seed, P.offset + (uint64_t)m * P.ld_rng + n0, P.thresh, keep);
-    }
-  }
+  if (epi_drops<EPI>() && P.thresh) kr.run(P, dpair, m, n0, keep);
   h16x4 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    float r;
-    if (EPI == MMS_EPI_RELU_DROP) r = keep[e] ? fmaxf(x[e], 0.f) * dscale : 0.f;
-    else if (EPI == MMS_EPI_DROP_RESID) r = (float)ax[e] + (keep[e] ? x[e] * dscale : 0.f);
-    else if (EPI == MMS_EPI_RELU_DROP_BWD) r = (float)ax[e] > 0.f ? x[e] * dscale : 0.f;
-    else r = x[e];
-    o[e] = (h16)r;
+    h16 o2 = (h16)0.f;   // (no supported form writes out2)
+    o[e] = (h16)epi_element<EPI>(v[e] * P.alpha + bv[e], (float)ax[e], 0.f, keep[e], dscale, o2);
   }
   return __builtin_bit_cast(pu32x2, o);
 }
@@ -92,7 +69,6 @@ __global__ void __launch_bounds__(NT, 2) gemm_persist_kernel(GemmP P, int tiles_
       (void*)P.B, (short)0, (int)(((long)(P.N - 1) * P.ldb + P.K) * 2), 0x00020000);
   const int nk = P.K / BK;   // host: K % 64 == 0, K > 0
   const float dscale = P.thresh ? 1.f / (1.f - P.p) : 1.f;
-  const bool drop_ok = ((P.offset & 1) == 0) && ((P.ld_rng & 1) == 0);
   h16* C = reinterpret_cast<h16*>(P.C);
 
   auto stage_a = [&](int s) { return smem + s * STAGE; };
@@ -196,24 +172,19 @@ __global__ void __launch_bounds__(NT, 2) gemm_persist_kernel(GemmP P, int tiles_
       for (int idx = 0; idx < NST; ++idx) store_one(idx);
     }
     // ---- this tile's epilogue, from the accumulators
-    PtDrop D;
-    D.fast = false;
-    D.hmix = 0;
-    D.pbase = 0;
-    if (epi_drops<EPI>() && P.thresh) {
-      const uint64_t cf = P.offset + (uint64_t)bm * P.ld_rng + bn;
-      const uint64_t cl = P.offset + (uint64_t)(bm + BMT - 1) * P.ld_rng + bn + BN - 1;
-      D.fast = drop_ok && mms_same_hi(cf, cl);
-      D.hmix = mms_hi_mix(P.seed, cf);
-      D.pbase = (uint32_t)(cf >> 1);
-    }
+    // the lane's 4 FRT runs: rows m0 + 16 i, columns n00 + 16 j .. + 3 (as reg_epilogue)
+    const int m0 = bm + wm * 16 * FRT + r16, n00 = bn + wn * 64 + 4 * q;
+    KeepRuns<4> kr;
+    if (epi_drops<EPI>() && P.thresh)
+      kr.init(P, P.offset + (uint64_t)m0 * P.ld_rng + n00,
+              P.offset + (uint64_t)(m0 + 16 * (FRT - 1)) * P.ld_rng + n00 + 51);
     float bv[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n0 = bn + wn * 64 + 16 * j + 4 * q;
 #pragma unroll
       for (int e = 0; e < 4; ++e) bv[j][e] = 0.f;
-      if (P.bias && EPI != MMS_EPI_RELU_DROP_BWD && n0 < P.N) {
+      if (epi_adds_bias<EPI>() && P.bias && n0 < P.N) {
         const h16x4 b4 = *reinterpret_cast<const h16x4*>(P.bias + n0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) bv[j][e] = (float)b4[e];
@@ -233,8 +204,7 @@ __global__ void __launch_bounds__(NT, 2) gemm_persist_kernel(GemmP P, int tiles_
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int n0 = bn + wn * 64 + 16 * j + 4 * q;
-        const uint32_t pair0 = D.pbase + (uint32_t)(((m - bm) * (long)P.ld_rng + (n0 - bn)) >> 1);
-        o[j] = pt_frag<EPI>(P, acc[i][j], bv[j], ax[j], D, pair0, m, n0, dscale);
+        o[j] = pt_frag<EPI>(P, acc[i][j], bv[j], ax[j], kr, (uint32_t)(8 * i) * (uint32_t)P.ld_rng + 8 * j, m, n0, dscale);
       }
       // pair fragments (0, 1) and (2, 3): lane row q ends up with 8 consecutive columns
 #pragma unroll

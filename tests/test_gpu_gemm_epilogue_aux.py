@@ -192,6 +192,92 @@ def test_batched_bit_identical(K_, routes):
     assert rel(y, ref + c0.float()) < TOL
 
 
+class _NarrowCase(_Case):
+    """_Case with C and out2 in ldc-wide buffers (columns N..ldc hold a sentinel) and the aux operands
+    in ldaux-wide ones; GATE's merged operand is 2 N + 4 wide (its second half starts at aux + N, so it
+    cannot live in an ldaux = N + 8 row; 2 N + 4 keeps ldaux % 8 == 4).  run() returns the whole C buffer."""
+    PAD = 7.0
+
+    def __init__(self, K_, M, N, Kd, ldc, ldaux, fixup):
+        super().__init__(K_, M, N, Kd)
+        self.ldc, self.fixup = ldc, fixup
+        g = torch.Generator(device="cuda").manual_seed(3 * M + N + Kd)
+        r = lambda *s: torch.randn(*s, device="cuda", generator=g)
+        self.res, self.h, self.z = (r(M, ldaux).half()[:, :N] for _ in range(3))
+        self.merge = r(M, 2 * N + 4).half()[:, :2 * N]
+        self.cbuf = torch.full((M, ldc), self.PAD, dtype=torch.float16, device="cuda")
+        self.o2buf = torch.full((M, ldc), self.PAD, dtype=torch.float16, device="cuda")
+        self.out, self.g = self.cbuf[:, :N], self.o2buf[:, :N]
+
+    def run(self, epi, *, bias=None, aux=None, out2=None, p=0.0, drop=(0, 0)):
+        M, N, Kd = self.M, self.N, self.Kd
+        self.K_.gemm(self.x, self.W, self.cbuf, M, N, Kd, lda=Kd, ldb=Kd, ldc=self.ldc, epi=epi, bias=bias, aux=aux,
+                     ldaux=(aux.stride(0) if aux is not None else 0), out2=out2,
+                     ldo2=(out2.stride(0) if out2 is not None else 0), p=p, seed=drop[0], offset=drop[1], ld_rng=N,
+                     fixup=self.fixup)
+        return torch.cat([self.cbuf, self.o2buf]) if out2 is not None else self.cbuf
+
+
+def _gelu_grad(z):
+    return 0.5 * (1 + torch.erf(z * 2 ** -0.5)) + z * torch.exp(-0.5 * z * z) * (2 * torch.pi) ** -0.5
+
+
+NARROW = [(17, 68, 64, 68, 76, "dma"), (17, 68, 64, 68, 76, "tall"), (17, 68, 512, 68, 76, "skinny"),
+          (17, 68, 512, 68, 76, "fixup"), (130, 70, 128, 72, 76, "dma"), (130, 70, 128, 72, 76, "tall")]
+
+
+@pytest.mark.parametrize("M,N,Kd,ldc,ldaux,route", NARROW)
+def test_narrow_store_operand_forms(K_, routes, M, N, Kd, ldc, ldaux, route):
+    """The 4- / 8-column store functions epilogue_store / epilogue_store8 (gemm_common.h), the only path
+    where vec16 == 0 and on N tails, under the forms that read a row operand or write out2.
+    (17, 68, .): ldc = 68 and ldaux = 76 are 4 mod 8, so vec16 == 0 and every group is 4-wide.
+    (130, 70, 128): ldc = 72; the forms without aux keep vec16 == 1 and a row is eight 8-wide groups, one
+    full 4-wide group (64..67) and a 2-element scalar tail (68, 69); with aux (ldaux = 76) all is 4-wide.
+    GATE is left out at N = 70: its second operand sits at aux + N and is read 4-wide, N % 4 == 0.
+    Routes (csrc/gemm.hip gemm_dispatch; N % 64 != 0, so reg_epilogue_ok() is false on all of them):
+      dma    short-M kernel off, unsplit: `if (dma_ok)` -> launch_dma<true, true> (tall_pick() returns 0
+             at these M), staged_epilogue -> epilogue_store8;
+      tall   the same with mms2ut_gemm_set_tall(2): `if (dma_ok && a_kc && b_kc && nz == 1)` ->
+             launch_tall<5>;
+      skinny K = 512 (K % 256 == 0), short-M kernel on, no split asked: `if (splitk == 1 &&
+             skinny_eligible(a))` -> launch_skinny (unsplit plan: no workspace is passed);
+      fixup  K = 512, short-M kernel off, kernels.gemm asks for 2 splits (_fixup_splits): `if (splitk > 1
+             && a->epi != MMS_EPI_F32)` -> fp32 slabs, then splitk_fixup_kernel -> epilogue_store8.
+    Per form: bits equal under mms2ut_gemm_set_epilogue(0 / 1), relative L2 against the fp32 torch
+    expression below TOL with the mask replayed by dropout_mask (one wrong keep bit of M N <= 9100
+    elements moves the L2 by >= 1 / sqrt(9100) = 1e-2), columns N..ldc of C and out2 untouched."""
+    E = K_
+    K_.call("mms2ut_gemm_set_skinny", 1 if route == "skinny" else 0)
+    K_.call("mms2ut_gemm_set_tall", 2 if route == "tall" else 1)
+    c = _NarrowCase(K_, M, N, Kd, ldc, ldaux, fixup=(route == "fixup"))
+    pre_b = c.pre + c.b.float()
+    sc = 1 / (1 - P_DROP)
+
+    def check(fn, ref, ref2=None):
+        y = _both(K_, fn)
+        assert (y[:, N:] == c.PAD).all()
+        assert rel(y[:M, :N], ref) < TOL
+        if ref2 is not None:
+            assert rel(y[M:, :N], ref2) < TOL
+
+    check(lambda: c.run(E.EPI_F16, bias=c.b), pre_b)
+    check(lambda: c.run(E.EPI_RELU_DROP_BWD, aux=c.h, p=P_DROP), c.pre * (c.h > 0) * sc)
+    check(c.acc, c.c0.float() + c.pre)
+    if N % 4 == 0:
+        gr = torch.sigmoid(pre_b)
+        o, t = c.merge[:, :N].float(), c.merge[:, N:].float()
+        check(lambda: c.run(E.EPI_GATE, bias=c.b, aux=c.merge, out2=c.g), (1 - gr) * t + gr * o, gr)
+    for drop in ((77, 7), (11, (1 << 33) - (M * N // 2 // 8 * 8 + 4))):   # odd offset; 2^33 inside the matrix
+        m = c.mask(drop)
+        check(lambda: c.run(E.EPI_RELU_DROP, bias=c.b, p=P_DROP, drop=drop), pre_b.relu() * m * sc)
+        check(lambda: c.run(E.EPI_DROP_RESID, bias=c.b, aux=c.res, p=P_DROP, drop=drop),
+              pre_b * m * sc + c.res.float())
+        check(lambda: c.run(E.EPI_GELU_DROP, bias=c.b, out2=c.g, p=P_DROP, drop=drop),
+              torch.nn.functional.gelu(pre_b) * m * sc, pre_b)
+        check(lambda: c.run(E.EPI_GELU_DROP_BWD, aux=c.z, p=P_DROP, drop=drop),
+              c.pre * m * sc * _gelu_grad(c.z.float()))
+
+
 def test_n1004_stays_staged(K_, routes):
     """N = 1004 in a 1024-column row: N % 64 != 0, so every wave of every block takes the staged path on
     unpermuted weight rows (a mixed choice races on the LDS slots, which only repeated runs expose)."""

@@ -106,8 +106,8 @@ def test_gemm_epilogues(K):
 @pytest.mark.parametrize("M,N,Kd", [(10000, 3072, 768), (12000, 768, 768), (5000, 768, 768), (2000, 768, 192),
                                     (333, 520, 256)])
 def test_gemm_dropout_masks_every_tile(K, M, N, Kd):
-    """The dropout keep flags of the fused GEMM epilogues — computed inside the k-loop on the fast
-    path (gemm_common.h epi_bits_step, round 6) or hashed in the epilogue (odd counter offset) — equal
+    """The dropout keep flags of the fused GEMM epilogues — one mixer per counter pair on the fast
+    path (gemm_common.h KeepRuns) or hashed counter by counter (odd counter offset) — equal
     the standalone dropout kernel's mask for the same counters, on every tile height (128 / 96 / 160
     / 192 rows) and for the ReLU, residual and GELU sites.  A bias of 30 keeps every activation
     positive, so the zero pattern of the output is the mask."""
