@@ -675,6 +675,65 @@ int mms2ut_hifigan_sizes(const mms2ut_hifigan* m, int64_t T_frames, int64_t* ws_
 int mms2ut_hifigan_fwd(const mms2ut_hifigan* m, const int64_t* codes, int T, const int64_t* cum,
                        int64_t T_frames, void* ws, float* wave, int* launches, hipStream_t stream);
 
+/* ---------------------------------------------------------------- wav2vec2 CTC transcription
+ * Forward-only kernels in front of and behind the transformer body of HF Wav2Vec2ForCTC
+ * (feat_extract_norm "layer", do_stable_layer_norm) -- csrc/asr.hip, asr.py.  Activations are
+ * time-major fp16 rows [T, C] as in the vocoder; all accumulation is fp32.
+ *
+ * mms2ut_wave_stats: stats[0] = mean, stats[1] = 1 / sqrt(var + eps) of x[0, n) (population variance,
+ * the mean squared deviation from the mean), reduced through per-block partial sums in double that
+ * every reader folds in the same order (no atomics).  ws: MMS_ASR_STAT_WS_DOUBLES doubles.       */
+#define MMS_ASR_STAT_PARTS      64
+#define MMS_ASR_STAT_WS_DOUBLES (2 * MMS_ASR_STAT_PARTS)
+int mms2ut_wave_stats(const float* x, int64_t n, float eps, double* ws, float* stats, hipStream_t stream);
+/* Feature-extractor layer 0 in one launch, T0 = (n - k) / stride + 1 frames:
+ *   y[t, c] = GELU(LayerNorm_c(bias[c] + sum_j ((x[t * stride + j] - stats[0]) * stats[1]) * w[j, c]))
+ * x fp32 [n]; w fp32 [k, C] (the Conv1d weight [C, 1, k] transposed); bias, ln_g, ln_b fp32 [C];
+ * y fp16 [T0, C], row stride ldy; GELU in the erf form.                                           */
+#define MMS_ASR_CONV0_MAX_C 512
+#define MMS_ASR_CONV0_MAX_K 16
+#define MMS_ASR_CONV0_MAX_S 16
+int mms2ut_asr_conv0(const float* x, int64_t n, const float* stats, const float* w, const float* bias,
+                     const float* ln_g, const float* ln_b, float eps, int k, int stride, int C, void* y,
+                     int64_t ldy, hipStream_t stream);
+/* Implicit-GEMM Conv1d with a stride and groups (no im2col image), one launch; group g reads the
+ * columns [g Cin, (g + 1) Cin) of x and writes the columns [g Cout, (g + 1) Cout) of y:
+ *   v[q, co] = bias[co] + sum_{j < taps, ci} x[q * stride + j - pad, ci] * W[co, ci, j]
+ *              (rows outside [0, T_in) read as zeros)
+ *   y[q, co] = v                          res NULL  (feature-extractor layers 1..)
+ *            = res[q, co] + GELU(v)       otherwise (the positional convolution)
+ * w: one image per group in the layout of mms2ut_conv1d_tm (vocoder.pack_conv_weight of the group's
+ * [Cout, Cin, taps] weight), w_group elements apart.  127 * stride + taps <= MMS_ASR_CONV_MAX_ROWS;
+ * (T_out - 1) * stride + taps <= T_in + 2 pad.                                                    */
+#define MMS_ASR_CONV_MAX_ROWS 264
+typedef struct {
+  const void* x;        /* fp16 [T_in, groups * Cin], row stride ldx */
+  int64_t ldx;
+  int T_in, Cin;        /* Cin, Cout: per group */
+  const void* w;        /* packed fp16 weight images */
+  int64_t w_group;      /* elements between the images of consecutive groups */
+  const float* bias;    /* fp32 [groups * Cout] or NULL */
+  void* y;              /* fp16 [T_out, groups * Cout], row stride ldy */
+  int64_t ldy;
+  int T_out, Cout;
+  int taps, stride, pad, groups;
+  const void* res;      /* fp16 [T_out, groups * Cout] or NULL, row stride ldres */
+  int64_t ldres;
+} mms2ut_asr_conv_args;
+int mms2ut_asr_conv(const mms2ut_asr_conv_args* a, hipStream_t stream);
+/* In place over fp16 rows [T, C] (row stride ld): x = GELU(LayerNorm(x; g, b fp32 [C], eps)).     */
+#define MMS_ASR_LN_MAX_C 1024
+int mms2ut_asr_ln_gelu(void* x, int64_t ld, int T, int C, const float* g, const float* b, float eps,
+                       hipStream_t stream);
+/* Greedy CTC decoding of B utterances, one block each.  logits fp32 [B, Tmax, ld >= V]; bias (fp32 [V]
+ * or NULL) is added in place first (the head's bias).  For utterance b with T = lens[b] frames (Tmax
+ * with lens NULL): ids[b, t] = argmax_v logits[b, t, v] (the lowest index on ties); out[b, 0..count[b])
+ * = the ids that differ from their predecessor and from `blank`, in order; bad[b] = 1 if any of its
+ * T x V logits is not finite, else 0.  ids, out int32 [B, Tmax]; count, bad int32 [B].             */
+int mms2ut_ctc_greedy(float* logits, int64_t ld, int V, int B, int Tmax, const int32_t* lens,
+                      const float* bias, int blank, int32_t* ids, int32_t* out, int32_t* count,
+                      int32_t* bad, hipStream_t stream);
+
 /* ---------------------------------------------------------------- transformer layers
  * One whole pre-LN transformer layer per call — SURVEY §8b "encoder / decoder layer fwd/bwd":
  *   MMS_LAYER_ENC: fairseq TransformerEncoderLayer (encoder_normalize_before; A5, reached from

@@ -162,6 +162,19 @@ class HifiGan(C.Structure):
                 ("post_w", vp), ("post_b", f32), ("post_k", i32), ("slope", f32), ("post_slope", f32)]
 
 
+ASR_STAT_WS_DOUBLES = 128                                # include/mms2ut.h MMS_ASR_*
+ASR_CONV0_MAX_C, ASR_CONV0_MAX_K, ASR_CONV0_MAX_S, ASR_CONV_MAX_ROWS, ASR_LN_MAX_C = 512, 16, 16, 264, 1024
+
+
+class AsrConvArgs(C.Structure):
+    """mms2ut_asr_conv_args (include/mms2ut.h): one strided / grouped implicit-GEMM Conv1d launch."""
+    _fields_ = [("x", vp), ("ldx", i64), ("T_in", i32), ("Cin", i32), ("w", vp), ("w_group", i64), ("bias", vp),
+                ("y", vp), ("ldy", i64), ("T_out", i32), ("Cout", i32), ("taps", i32), ("stride", i32), ("pad", i32),
+                ("groups", i32), ("res", vp), ("ldres", i64)]
+
+
+ASR_CONV_ARGS = _packer(AsrConvArgs)
+
 # name -> (restype, argtypes); every symbol include/mms2ut.h declares
 SIGNATURES = {
     "mms2ut_last_error": (C.c_char_p, []),
@@ -260,6 +273,11 @@ SIGNATURES = {
                                         vp, vp, vp]),
     "mms2ut_hifigan_sizes": (i32, [vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mms2ut_hifigan_fwd": (i32, [vp, vp, i32, vp, i64, vp, vp, C.POINTER(C.c_int), vp]),
+    "mms2ut_wave_stats": (i32, [vp, i64, f32, vp, vp, vp]),
+    "mms2ut_asr_conv0": (i32, [vp, i64, vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, i64, vp]),
+    "mms2ut_asr_conv": (i32, [vp, vp]),   # ASR_CONV_ARGS.pack(...) bytes
+    "mms2ut_asr_ln_gelu": (i32, [vp, i64, i32, i32, vp, vp, f32, vp]),
+    "mms2ut_ctc_greedy": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "mms2ut_layer_arena": (i32, [vp, vp, vp]),
     "mms2ut_layer_scratch": (i32, [vp, f32, vp, vp]),
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),

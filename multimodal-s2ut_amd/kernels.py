@@ -1527,4 +1527,126 @@ def var_pred_layer(x, w, b, ln_g, ln_b, *, idx=None, proj=None, eps=1e-5):
     return out if proj is None else (logd, dur)
 
 
+# ============================================================================ wav2vec2 CTC transcription
+
+def _f32c(t, name, n=None):
+    _chk(t, torch.float32)
+    if not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f"{name}: contiguous fp32 tensor of {n} elements expected, got {tuple(t.shape)}")
+
+
+def wave_stats(x, eps=1e-7):
+    """fp32 [2] = (mean, 1 / sqrt(var + eps)) of the fp32 waveform x [n] (population variance)."""
+    _f32c(x, "wave_stats x")
+    if x.dim() != 1 or x.numel() < 1:
+        raise ValueError(f"wave_stats: a non-empty 1-D waveform expected, got {tuple(x.shape)}")
+    ws = torch.empty(_lib.ASR_STAT_WS_DOUBLES, dtype=torch.float64, device=x.device)
+    stats = torch.empty(2, dtype=torch.float32, device=x.device)
+    call("mms2ut_wave_stats", x.data_ptr(), x.numel(), float(eps), ws.data_ptr(), stats.data_ptr(), _s())
+    return stats
+
+
+def asr_conv0(x, stats, w, bias, ln_g, ln_b, stride, eps=1e-5):
+    """Feature-extractor layer 0: fp32 waveform x [n], normalised by stats (wave_stats) as it is read,
+    Conv1d(1 -> C, k, stride) + LayerNorm over C + GELU -> fp16 [(n - k) // stride + 1, C]; w fp32 [k, C]."""
+    _f32c(x, "asr_conv0 x")
+    _f32c(stats, "asr_conv0 stats", 2)
+    _chk(w, torch.float32)
+    if x.dim() != 1 or w.dim() != 2 or not w.is_contiguous():
+        raise ValueError("asr_conv0: x [n] and a contiguous w [k, C] expected")
+    k, Cc = w.shape
+    for t, nm in ((bias, "bias"), (ln_g, "ln_g"), (ln_b, "ln_b")):
+        _f32c(t, "asr_conv0 " + nm, Cc)
+    if x.numel() < k:
+        raise ValueError(f"asr_conv0: {x.numel()} samples are fewer than the kernel's {k}")
+    T0 = (x.numel() - k) // stride + 1
+    y = torch.empty(T0, Cc, dtype=F16, device=x.device)
+    call("mms2ut_asr_conv0", x.data_ptr(), x.numel(), stats.data_ptr(), w.data_ptr(), bias.data_ptr(), ln_g.data_ptr(),
+         ln_b.data_ptr(), float(eps), int(k), int(stride), int(Cc), y.data_ptr(), y.stride(0), _s())
+    return y
+
+
+def asr_conv(x, w_packed, bias, Cout, taps, stride=1, pad=0, groups=1, *, T_out=None, res=None, out=None):
+    """Strided / grouped implicit-GEMM Conv1d over time-major fp16 rows: x [T, groups * Cin] ->
+    [T_out, Cout] (Cout over all groups; T_out defaults to (T + 2 pad - taps) // stride + 1).  w_packed:
+    the groups' vocoder.pack_conv_weight images one after the other.  res: out = res + GELU(conv + bias)."""
+    _chk(x)
+    _chk(w_packed)
+    _rows16(x, "asr_conv x")
+    T, Cin_all = x.shape
+    if groups < 1 or Cin_all % groups or Cout % groups:
+        raise ValueError(f"asr_conv: {groups} groups do not divide the widths {Cin_all} -> {Cout}")
+    Cin, Cog = Cin_all // groups, Cout // groups
+    full = (T + 2 * pad - taps) // stride + 1
+    T_out = full if T_out is None else int(T_out)
+    if T_out < 1 or T_out > full:
+        raise ValueError(f"asr_conv: {T_out} outputs from T {T}, taps {taps}, stride {stride}, pad {pad} (at most {full})")
+    per = 0
+    if Cin % 8 == 0 and Cin >= 8 and Cog % 8 == 0 and Cog >= 8:
+        per = conv1d_tm_packed_halves(Cin, Cog, taps)
+        if not w_packed.is_contiguous() or w_packed.numel() != groups * per:
+            raise ValueError(f"asr_conv: packed weight of {w_packed.numel()} elements for {groups} x (Cin {Cin}, "
+                             f"Cout {Cog}, taps {taps})")
+    if out is None:
+        out = torch.empty(T_out, Cout, dtype=F16, device=x.device)
+    _chk(out)
+    _rows16(out, "asr_conv out")
+    if tuple(out.shape) != (T_out, Cout):
+        raise ValueError(f"asr_conv: out {tuple(out.shape)}, expected {(T_out, Cout)}")
+    # a block stages input rows whose outputs belong to its neighbours: out must not overlap x (res may be x)
+    x0, o0 = x.data_ptr(), out.data_ptr()
+    x1, o1 = x0 + ((T - 1) * x.stride(0) + Cin_all) * 2, o0 + ((T_out - 1) * out.stride(0) + Cout) * 2
+    if x0 < o1 and o0 < x1:
+        raise ValueError("asr_conv: out overlaps x; the convolution cannot run in place")
+    if bias is not None:
+        _f32c(bias, "asr_conv bias", Cout)
+    if res is not None:
+        _chk(res)
+        _rows16(res, "asr_conv res")
+        if tuple(res.shape) != (T_out, Cout):
+            raise ValueError(f"asr_conv: res {tuple(res.shape)}, expected {(T_out, Cout)}")
+    call("mms2ut_asr_conv", _lib.ASR_CONV_ARGS.pack(
+        x.data_ptr(), x.stride(0), T, Cin, w_packed.data_ptr(), per, _p(bias) or 0, out.data_ptr(), out.stride(0),
+        T_out, Cog, int(taps), int(stride), int(pad), int(groups), _p(res) or 0,
+        res.stride(0) if res is not None else 0), _s())
+    return out
+
+
+def asr_ln_gelu(x, g, b, eps=1e-5):
+    """x = GELU(LayerNorm(x)) in place over fp16 rows [T, C]; g, b fp32 [C]."""
+    _chk(x)
+    _rows16(x, "asr_ln_gelu x")
+    T, Cc = x.shape
+    _f32c(g, "asr_ln_gelu g", Cc)
+    _f32c(b, "asr_ln_gelu b", Cc)
+    if T:
+        call("mms2ut_asr_ln_gelu", x.data_ptr(), x.stride(0), T, Cc, g.data_ptr(), b.data_ptr(), float(eps), _s())
+    return x
+
+
+def ctc_greedy(logits, V, blank, lens=None, bias=None):
+    """Greedy CTC decode of fp32 logits [B, Tmax, ld >= V] (bias fp32 [V], when given, is added in place
+    first) -> (ids int32 [B, Tmax] the per-frame argmax, out int32 [B, Tmax] the collapsed non-blank ids,
+    count int32 [B], bad int32 [B]: 1 where an utterance has a non-finite logit).  lens int32 [B]."""
+    _chk(logits, torch.float32)
+    if logits.dim() != 3 or not logits.is_contiguous():
+        raise ValueError(f"ctc_greedy: contiguous logits [B, Tmax, ld] expected, got {tuple(logits.shape)}")
+    B, Tmax, ld = logits.shape
+    if not (1 <= V <= ld) or B < 1 or Tmax < 1:
+        raise ValueError(f"ctc_greedy: V {V} outside [1, {ld}] or an empty batch {tuple(logits.shape)}")
+    if lens is not None:
+        _chk(lens, torch.int32)
+        assert lens.is_contiguous() and lens.numel() == B
+    if bias is not None:
+        _f32c(bias, "ctc_greedy bias", V)
+    dev = logits.device
+    ids = torch.zeros(B, Tmax, dtype=torch.int32, device=dev)
+    out = torch.zeros(B, Tmax, dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    bad = torch.empty(B, dtype=torch.int32, device=dev)
+    call("mms2ut_ctc_greedy", logits.data_ptr(), ld, int(V), B, Tmax, _p(lens), _p(bias), int(blank), ids.data_ptr(),
+         out.data_ptr(), count.data_ptr(), bad.data_ptr(), _s())
+    return ids, out, count, bad
+
+
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]

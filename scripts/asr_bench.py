@@ -1,0 +1,156 @@
+"""Timing of the wav2vec2 CTC transcription step (multimodal-s2ut_amd/asr.py) at the released large
+configuration with seeded random weights: one 5 s utterance alone and 16 of them in one encoder batch.
+
+    python scripts/asr_bench.py [--seconds 5] [--batch 16] [--layers 24] [--repeats 20] [--out FILE]
+
+HIP events on the stream the kernels run on, warm-up first, median (min .. max) of the repeats.  The FLOPs
+are the algorithm's, computed from the shapes: 2 * T_out * Cout * Cin * k per convolution.  Every time is
+event time around one call, host launch gaps included, so the TF/s printed are event-time rates (lower
+bounds on the kernels' own rates); a kernel rate needs a kernel trace, which this script does not take.  The CPU line
+is tests/asr_ref.py's fp32 restatement on the host's threads at the same shape, one run."""
+import argparse
+import importlib
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def _events(n):
+    return [torch.cuda.Event(enable_timing=True) for _ in range(n)]
+
+
+def timed(fn, warmup, repeats):
+    """Median / min / max ms of fn() on the current stream."""
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(repeats):
+        a, b = _events(2)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--seconds", type=float, default=5.0)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--layers", type=int, default=24)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
+    ap.add_argument("--out", default=None, help="also write the report here")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("asr_bench needs a GPU: a CPU run gives no timing")
+    import asr_ref as AR
+    A = importlib.import_module("multimodal-s2ut_amd.asr")
+    K = importlib.import_module("multimodal-s2ut_amd.kernels")
+
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    cfg = dict(AR.WIDE, num_hidden_layers=args.layers)
+    sd = AR.make_state_dict(cfg, seed=0)
+    m = A.Wav2Vec2CTC(sd, cfg, AR.VOCAB, device="cuda:0")
+    n = int(args.seconds * 16000)
+    waves = [AR.to_float(AR.make_wave(n, 100 + i)) for i in range(args.batch)]
+    xs = [m._wave(w) for w in waves]
+    T = AR.frame_count(n)
+    d, cg, pk = cfg["hidden_size"], cfg["hidden_size"] // cfg["num_conv_pos_embedding_groups"], cfg["num_conv_pos_embeddings"]
+    Ts = A.frame_counts(n, m.kernels, m.strides)
+    cins = [1] + list(cfg["conv_dim"][:-1])
+    fl_layers = [2.0 * t * co * ci * k for t, co, ci, k in zip(Ts, cfg["conv_dim"], cins, m.kernels)]
+    fl_ext, fl_mfma, fl_pos = sum(fl_layers), sum(fl_layers[1:]), 2.0 * T * d * cg * pk
+    say(f"wav2vec2 CTC: d {d}, {cfg['num_attention_heads']} heads, FFN {cfg['intermediate_size']}, {args.layers} layers, "
+        f"conv {cfg['conv_dim'][0]}; {args.seconds:g} s = {n} samples -> {T} frames; random weights")
+    say(f"algorithmic FLOPs per utterance: extractor {fl_ext / 1e9:.2f} G (layers 1.. on MFMA {fl_mfma / 1e9:.2f} G), "
+        f"positional conv {fl_pos / 1e9:.2f} G")
+
+    def report(name, t, extra=""):
+        say(f"{name:<52s}{t[0]:9.3f} ms  [{t[1]:.3f} .. {t[2]:.3f}] {extra}")
+
+    w, r = args.warmup, args.repeats
+    x = xs[0]
+    # ---- stages, one utterance
+    h_ext = m.extract(x)
+    h_pos = m.positional(h_ext)
+    Hb1 = h_pos.unsqueeze(0)
+    X1 = m.layers_forward(Hb1)
+    report("1 utt: feature extractor + projection", t_ext := timed(lambda: m.extract(x), w, r))
+    report("1 utt: positional conv", t_pos := timed(lambda: m.positional(h_ext), w, r),
+           f"{fl_pos / t_pos[0] / 1e9:.2f} TF/s over event time")
+    report("1 utt: encoder layers", t_enc := timed(lambda: m.layers_forward(Hb1), w, r))
+
+    def head_decode(Xr, B, lens32, lens):
+        logits = m.head(Xr, B, T)
+        _, out, count, bad = K.ctc_greedy(logits, m.V, m.blank, lens32, m.head_b)
+        return m._texts(lens, out, count, bad, None)          # the device-to-host copy of the ids ends the stage
+
+    report("1 utt: final LN + head + CTC greedy + ids to host", t_head := timed(lambda: head_decode(X1, 1, None, [T]), w, r))
+    # the six MFMA convolutions of the extractor alone, on the inputs they see
+    stats = K.wave_stats(x, A.NORM_EPS)
+    c0 = m.conv[0]
+    ins, h = [], K.asr_conv0(x, stats, c0.w, c0.b, c0.g, c0.be, c0.stride, A.CONV_LN_EPS)
+    for c in m.conv[1:]:
+        ins.append(h)
+        h = K.asr_ln_gelu(K.asr_conv(h, c.w, c.b, c.cout, c.k, c.stride), c.g, c.be, A.CONV_LN_EPS)
+
+    def convs():
+        for c, hin in zip(m.conv[1:], ins):
+            K.asr_conv(hin, c.w, c.b, c.cout, c.k, c.stride)
+
+    report("1 utt: extractor layers 1.. convolutions alone", t_c := timed(convs, w, r), f"{fl_mfma / t_c[0] / 1e9:.2f} TF/s over event time")
+    report("1 utt: layer 0 (stats + conv + LN + GELU) alone",
+           timed(lambda: K.asr_conv0(x, K.wave_stats(x, A.NORM_EPS), c0.w, c0.b, c0.g, c0.be, c0.stride, A.CONV_LN_EPS), w, r),
+           f"{Ts[0] * c0.cout * 2 / 1e6:.1f} MB written")
+    report("1 utt: transcribe() end to end", t_one := timed(lambda: m.transcribe(waves[0]), w, r),
+           f"real-time factor {t_one[0] / 1e3 / args.seconds:.5f}")
+    # ---- the batch
+    B = args.batch
+    if B > 1:
+        t_b = timed(lambda: m.transcribe_many(waves, B), w, r)
+        report(f"{B} utts: transcribe_many() end to end", t_b,
+               f"{t_b[0] / B:.3f} ms per utterance, real-time factor {t_b[0] / 1e3 / (B * args.seconds):.5f}")
+        lens32 = torch.tensor([T] * B, dtype=torch.int32, device="cuda:0")
+        Hb = torch.zeros(B, T, d, dtype=torch.float16, device="cuda:0")
+
+        def feats():
+            for b in range(B):
+                m.features(xs[b], out=Hb[b])
+
+        report(f"{B} utts: extractor + projection + positional conv", timed(feats, w, r))
+        XB = m.layers_forward(Hb, lens32)
+        report(f"{B} utts: encoder layers, packed", t_eb := timed(lambda: m.layers_forward(Hb, lens32), w, r),
+               f"{t_eb[0] / B:.3f} ms per utterance")
+        report(f"{B} utts: final LN + head + CTC greedy + ids to host",
+               timed(lambda: head_decode(XB, B, lens32, [T] * B), w, r))
+    if not args.no_cpu:
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            AR.forward(sd, cfg, waves[0])
+        dt = time.perf_counter() - t0
+        say(f"CPU fp32 restatement, 1 utt, {torch.get_num_threads()} threads, one run: {dt * 1e3:.0f} ms "
+            f"(real-time factor {dt / args.seconds:.3f})")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
