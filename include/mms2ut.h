@@ -701,7 +701,8 @@ int mms2ut_asr_conv0(const float* x, int64_t n, const float* stats, const float*
  *   v[q, co] = bias[co] + sum_{j < taps, ci} x[q * stride + j - pad, ci] * W[co, ci, j]
  *              (rows outside [0, T_in) read as zeros)
  *   y[q, co] = v                          res NULL  (feature-extractor layers 1..)
- *            = res[q, co] + GELU(v)       otherwise (the positional convolution)
+ *            = GELU(v)                    res NULL and gelu set (HuBERT's extractor layers 1..: no norm)
+ *            = res[q, co] + GELU(v)       res given (the positional convolution)
  * w: one image per group in the layout of mms2ut_conv1d_tm (vocoder.pack_conv_weight of the group's
  * [Cout, Cin, taps] weight), w_group elements apart.  127 * stride + taps <= MMS_ASR_CONV_MAX_ROWS;
  * (T_out - 1) * stride + taps <= T_in + 2 pad.                                                    */
@@ -719,6 +720,7 @@ typedef struct {
   int taps, stride, pad, groups;
   const void* res;      /* fp16 [T_out, groups * Cout] or NULL, row stride ldres */
   int64_t ldres;
+  int gelu;             /* with res NULL: y = GELU(v), rounded to fp16 once, after the GELU */
 } mms2ut_asr_conv_args;
 int mms2ut_asr_conv(const mms2ut_asr_conv_args* a, hipStream_t stream);
 /* In place over fp16 rows [T, C] (row stride ld): x = GELU(LayerNorm(x; g, b fp32 [C], eps)).     */
@@ -733,6 +735,42 @@ int mms2ut_asr_ln_gelu(void* x, int64_t ld, int T, int C, const float* g, const 
 int mms2ut_ctc_greedy(float* logits, int64_t ld, int V, int B, int Tmax, const int32_t* lens,
                       const float* bias, int blank, int32_t* ids, int32_t* out, int32_t* count,
                       int32_t* bad, hipStream_t stream);
+
+/* ---------------------------------------------------------------- speech-to-unit quantisation
+ * HF HubertModel (feat_extract_norm "group", post-LN encoder) features and their nearest k-means
+ * centroid -- csrc/units.hip, units.py.  Extractor layers 1.. and the positional convolution are
+ * mms2ut_asr_conv (gelu / res), the layers run on the GEMM, LayerNorm and attention kernels.
+ *
+ * Layer 0, T0 = (n - k) / stride + 1 frames:
+ *   v[t, c] = bias[c] + sum_j xn[t * stride + j] * w[j, c],  xn = (x - stats[0]) * stats[1] or x (stats NULL)
+ *   y[t, c] = GELU((v[t, c] - mean_c) * rstd_c * gn_g[c] + gn_b[c])
+ * mean_c and rstd_c = 1 / sqrt(var_c + eps): the mean and biased variance of v[:, c] over all T0 frames
+ * (GroupNorm with one group per channel), from per-slice sums of v and v^2 in double that are added in
+ * slice order (no atomics).  bias may be NULL.  ws: MMS_HUBERT_GN_PARTS * C * 2 doubles.  mr fp32
+ * [C, 2] receives (mean_c, rstd_c).  w fp32 [k, C]; y fp16 [T0, C], row stride ldy.  Limits as
+ * mms2ut_asr_conv0.                                                                                 */
+#define MMS_HUBERT_GN_PARTS 256
+int mms2ut_hubert_conv0(const float* x, int64_t n, const float* stats, const float* w, const float* bias,
+                        const float* gn_g, const float* gn_b, float eps, int k, int stride, int C, double* ws,
+                        float* mr, void* y, int64_t ldy, hipStream_t stream);
+/* Nearest centroid of fp16 rows X [R, d] (row stride ldx): argmin_c cnorm[c] - 2 x . C_c over c < Kc,
+ * the lowest index on ties.  Each centroid is given as two fp16 images of round_up(Kc, 16) rows of d
+ * (rows past Kc: anything finite, they take no part): c_hi = fp16(C), c_lo = fp16((C - c_hi) *
+ * MMS_KMEANS_LO_SCALE); x . C = x . c_hi + (x . c_lo) / MMS_KMEANS_LO_SCALE, both sums in fp32.
+ * d: a multiple of 8.  The centroid axis is cut into chunks of `chunk` (a multiple of 64); chunk ch
+ * writes its best (score, index) of row r to pscore / pidx [ch * R + r].  mms2ut_kmeans_chunks gives
+ * the chunk the library would choose (chunk 0) or checks a given one, and the number of chunks.
+ * mms2ut_kmeans_fold, one block per utterance of a packed batch (R = B * Tmax, T = lens[b] or Tmax
+ * frames): code[b, t] = the best index over the chunks in chunk order; merged[b, 0..count[b]) = the
+ * codes that differ from their predecessor; bad[b] = 1 if the best score of any of its frames is not
+ * finite.  code, merged int32 [B, Tmax]; count, bad int32 [B].                                     */
+#define MMS_KMEANS_LO_SCALE 2048
+#define MMS_KMEANS_SMALL_BLOCKS 512
+int mms2ut_kmeans_chunks(int R, int Kc, int chunk, int* chunk_out, int* nchunks);
+int mms2ut_kmeans_assign(const void* X, int64_t ldx, int R, int d, const void* c_hi, const void* c_lo,
+                         const float* cnorm, int Kc, int chunk, float* pscore, int32_t* pidx, hipStream_t stream);
+int mms2ut_kmeans_fold(const float* pscore, const int32_t* pidx, int nchunks, int B, int Tmax, const int32_t* lens,
+                       int32_t* code, int32_t* merged, int32_t* count, int32_t* bad, hipStream_t stream);
 
 /* ---------------------------------------------------------------- transformer layers
  * One whole pre-LN transformer layer per call — SURVEY §8b "encoder / decoder layer fwd/bwd":

@@ -170,10 +170,11 @@ class AsrConvArgs(C.Structure):
     """mms2ut_asr_conv_args (include/mms2ut.h): one strided / grouped implicit-GEMM Conv1d launch."""
     _fields_ = [("x", vp), ("ldx", i64), ("T_in", i32), ("Cin", i32), ("w", vp), ("w_group", i64), ("bias", vp),
                 ("y", vp), ("ldy", i64), ("T_out", i32), ("Cout", i32), ("taps", i32), ("stride", i32), ("pad", i32),
-                ("groups", i32), ("res", vp), ("ldres", i64)]
+                ("groups", i32), ("res", vp), ("ldres", i64), ("gelu", i32)]
 
 
 ASR_CONV_ARGS = _packer(AsrConvArgs)
+HUBERT_GN_PARTS, KMEANS_LO_SCALE = 256, 2048              # include/mms2ut.h MMS_HUBERT_GN_PARTS, MMS_KMEANS_LO_SCALE
 
 # name -> (restype, argtypes); every symbol include/mms2ut.h declares
 SIGNATURES = {
@@ -278,6 +279,10 @@ SIGNATURES = {
     "mms2ut_asr_conv": (i32, [vp, vp]),   # ASR_CONV_ARGS.pack(...) bytes
     "mms2ut_asr_ln_gelu": (i32, [vp, i64, i32, i32, vp, vp, f32, vp]),
     "mms2ut_ctc_greedy": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "mms2ut_hubert_conv0": (i32, [vp, i64, vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, i64, vp]),
+    "mms2ut_kmeans_chunks": (i32, [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mms2ut_kmeans_assign": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "mms2ut_kmeans_fold": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mms2ut_layer_arena": (i32, [vp, vp, vp]),
     "mms2ut_layer_scratch": (i32, [vp, f32, vp, vp]),
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),

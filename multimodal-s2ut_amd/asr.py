@@ -85,11 +85,12 @@ def receptive_field(kernels, strides):
     return r
 
 
-def fold_pos_conv_weight_norm(sd):
+def fold_pos_conv_weight_norm(sd, prefix="wav2vec2."):
     """State dict with the positional convolution's weight norm folded (weight_norm(dim=2): w = g v / |v|,
     the norm over dims (0, 1) of each tap).  Accepts ``weight_g / weight_v`` and
-    ``parametrizations.weight.original0 / original1``; a plain ``weight`` passes through."""
-    base = "wav2vec2.encoder.pos_conv_embed.conv."
+    ``parametrizations.weight.original0 / original1``; a plain ``weight`` passes through.  prefix: what
+    the checkpoint puts in front of ``encoder.`` ("wav2vec2.", "hubert." or "")."""
+    base = prefix + "encoder.pos_conv_embed.conv."
     out = dict(sd)
     for gk, vk in (("weight_g", "weight_v"), ("parametrizations.weight.original0", "parametrizations.weight.original1")):
         if base + vk in sd:

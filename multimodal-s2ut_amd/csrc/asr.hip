@@ -16,8 +16,9 @@
 //                      split of K over the waves when the grid is small).  The operand row of output q,
 //                      tap j is input row stride * q + j - pad, read from the block's staged rows in
 //                      LDS; the reduction runs over (tap, cin).  blockIdx.z is the group.  Epilogue:
-//                      y = acc + bias (the extractor's layers 1..) or y = res + GELU(acc + bias) (the
-//                      positional convolution: 128 taps, 16 groups, K = 8192 per group).
+//                      y = acc + bias (the extractor's layers 1..), y = GELU(acc + bias) (HuBERT's, which
+//                      have no norm) or y = res + GELU(acc + bias) (the positional convolution: 128
+//                      taps, 16 groups, K = 8192 per group).
 //   asr_ln_gelu        in place over fp16 rows: GELU(LayerNorm(x)); one wave per row.  The extractor's
 //                      LayerNorm spans all C output channels of a frame and a conv block owns 64 of
 //                      them, so it runs as this row kernel behind the convolution.
@@ -279,6 +280,9 @@ __global__ void __launch_bounds__(AC_THREADS) asr_conv_kernel(const mms2ut_asr_c
         const h16x4 rv = *reinterpret_cast<const h16x4*>(res + (long)q * a.ldres + co);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (float)rv[e] + gelu_erf(v[e]);
+      } else if (a.gelu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
       }
       h16x4 o;
 #pragma unroll

@@ -1566,10 +1566,13 @@ def asr_conv0(x, stats, w, bias, ln_g, ln_b, stride, eps=1e-5):
     return y
 
 
-def asr_conv(x, w_packed, bias, Cout, taps, stride=1, pad=0, groups=1, *, T_out=None, res=None, out=None):
+def asr_conv(x, w_packed, bias, Cout, taps, stride=1, pad=0, groups=1, *, T_out=None, res=None, out=None, gelu=False):
     """Strided / grouped implicit-GEMM Conv1d over time-major fp16 rows: x [T, groups * Cin] ->
     [T_out, Cout] (Cout over all groups; T_out defaults to (T + 2 pad - taps) // stride + 1).  w_packed:
-    the groups' vocoder.pack_conv_weight images one after the other.  res: out = res + GELU(conv + bias)."""
+    the groups' vocoder.pack_conv_weight images one after the other.  res: out = res + GELU(conv + bias).
+    gelu (without res): out = GELU(conv + bias), rounded once."""
+    if gelu and res is not None:
+        raise ValueError("asr_conv: gelu selects the epilogue without a residual; with res the GELU is implied")
     _chk(x)
     _chk(w_packed)
     _rows16(x, "asr_conv x")
@@ -1608,7 +1611,7 @@ def asr_conv(x, w_packed, bias, Cout, taps, stride=1, pad=0, groups=1, *, T_out=
     call("mms2ut_asr_conv", _lib.ASR_CONV_ARGS.pack(
         x.data_ptr(), x.stride(0), T, Cin, w_packed.data_ptr(), per, _p(bias) or 0, out.data_ptr(), out.stride(0),
         T_out, Cog, int(taps), int(stride), int(pad), int(groups), _p(res) or 0,
-        res.stride(0) if res is not None else 0), _s())
+        res.stride(0) if res is not None else 0, 1 if gelu else 0), _s())
     return out
 
 
@@ -1647,6 +1650,98 @@ def ctc_greedy(logits, V, blank, lens=None, bias=None):
     call("mms2ut_ctc_greedy", logits.data_ptr(), ld, int(V), B, Tmax, _p(lens), _p(bias), int(blank), ids.data_ptr(),
          out.data_ptr(), count.data_ptr(), bad.data_ptr(), _s())
     return ids, out, count, bad
+
+
+# ============================================================================ speech-to-unit quantisation
+
+def hubert_conv0(x, stats, w, bias, gn_g, gn_b, stride, eps=1e-5, *, return_stats=False):
+    """HuBERT's feature-extractor layer 0: fp32 waveform x [n] (normalised by stats = wave_stats(x) as it
+    is read; stats None: as it is), Conv1d(1 -> C, k, stride) (+ bias, or None), GroupNorm with one group
+    per channel over all frames, GELU -> fp16 [(n - k) // stride + 1, C]; w fp32 [k, C].  return_stats:
+    also the fp32 [C, 2] per-channel (mean, 1 / sqrt(var + eps)) the normalisation used."""
+    _f32c(x, "hubert_conv0 x")
+    if stats is not None:
+        _f32c(stats, "hubert_conv0 stats", 2)
+    _chk(w, torch.float32)
+    if x.dim() != 1 or w.dim() != 2 or not w.is_contiguous():
+        raise ValueError("hubert_conv0: x [n] and a contiguous w [k, C] expected")
+    k, Cc = w.shape
+    for t, nm in ((gn_g, "gn_g"), (gn_b, "gn_b")) + (((bias, "bias"),) if bias is not None else ()):
+        _f32c(t, "hubert_conv0 " + nm, Cc)
+    if x.numel() < k:
+        raise ValueError(f"hubert_conv0: {x.numel()} samples are fewer than the kernel's {k}")
+    T0 = (x.numel() - k) // stride + 1
+    y = torch.empty(T0, Cc, dtype=F16, device=x.device)
+    ws = torch.empty(_lib.HUBERT_GN_PARTS * Cc * 2, dtype=torch.float64, device=x.device)
+    mr = torch.empty(Cc, 2, dtype=torch.float32, device=x.device)
+    call("mms2ut_hubert_conv0", x.data_ptr(), x.numel(), _p(stats), w.data_ptr(), _p(bias), gn_g.data_ptr(),
+         gn_b.data_ptr(), float(eps), int(k), int(stride), int(Cc), ws.data_ptr(), mr.data_ptr(), y.data_ptr(),
+         y.stride(0), _s())
+    return (y, mr) if return_stats else y
+
+
+def kmeans_pack(centroids):
+    """fp32 centroids [Kc, d] (host or device) -> (c_hi, c_lo fp16 [round_up(Kc, 16), d], cnorm fp32 [Kc]) for
+    kmeans_assign, on the centroids' device: c_hi = fp16(C), c_lo = fp16((C - c_hi) * 2^11), so that
+    c_hi + c_lo / 2^11 carries 22 bits of C; cnorm = |C_c|^2 summed in float64."""
+    Cm = centroids.detach().to(torch.float32)
+    if Cm.dim() != 2 or Cm.shape[0] < 1 or Cm.shape[1] % 8 or Cm.shape[1] < 8:
+        raise ValueError(f"kmeans_pack: centroids [Kc >= 1, d a multiple of 8] expected, got {tuple(Cm.shape)}")
+    if not bool(torch.isfinite(Cm).all()) or float(Cm.abs().max()) > 65504.0:
+        raise ValueError("kmeans_pack: centroids must be finite and within fp16's range")
+    Kc, d = Cm.shape
+    hi = torch.zeros(round_up(Kc, 16), d, dtype=F16, device=Cm.device)
+    lo = torch.zeros_like(hi)
+    hi[:Kc] = Cm.half()
+    lo[:Kc] = ((Cm - hi[:Kc].float()) * float(_lib.KMEANS_LO_SCALE)).half()
+    return hi, lo, Cm.double().pow(2).sum(1).float().contiguous()
+
+
+def kmeans_chunks(R, Kc, chunk=None):
+    """(chunk, number of chunks) of the centroid axis for R rows: the library's choice, or a given chunk checked."""
+    c, n = _lib.C.c_int(0), _lib.C.c_int(0)
+    call("mms2ut_kmeans_chunks", int(R), int(Kc), int(chunk or 0), _lib.C.byref(c), _lib.C.byref(n))
+    return c.value, n.value
+
+
+def kmeans_assign(X, c_hi, c_lo, cnorm, lens=None, *, chunk=None):
+    """Nearest centroid of every frame of fp16 X [B, Tmax, d] (or [T, d]: one utterance) against
+    kmeans_pack's images: argmin_c |C_c|^2 - 2 x . C_c, the lowest index on ties, in an MFMA GEMM that
+    never stores the scores.  -> (code int32 [B, Tmax], merged int32 [B, Tmax]: the codes with runs
+    collapsed, count int32 [B], bad int32 [B]: 1 where a frame's best score is not finite).  lens int32
+    [B]: rows past an utterance's length (anything finite) get no code.  chunk: the centroids per block
+    (a multiple of 64), by default chosen so that few rows still fill the chip."""
+    _chk(X)
+    if X.dim() == 2:
+        X = X.unsqueeze(0)
+    if X.dim() != 3 or not X.is_contiguous() or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"kmeans_assign: contiguous X [B, Tmax, d] expected, got {tuple(X.shape)}")
+    B, Tmax, d = X.shape
+    _chk(c_hi)
+    _chk(c_lo)
+    Kc = cnorm.numel()
+    _f32c(cnorm, "kmeans_assign cnorm")
+    shape = (round_up(Kc, 16), d)
+    if Kc < 1 or tuple(c_hi.shape) != shape or tuple(c_lo.shape) != shape or not c_hi.is_contiguous() \
+            or not c_lo.is_contiguous():
+        raise ValueError(f"kmeans_assign: centroid images {tuple(c_hi.shape)}, {tuple(c_lo.shape)}; {Kc} centroids of "
+                         f"width {d} need contiguous {shape} (kmeans_pack)")
+    if lens is not None:
+        _chk(lens, torch.int32)
+        assert lens.is_contiguous() and lens.numel() == B
+    R, dev = B * Tmax, X.device
+    chunk, nchunks = kmeans_chunks(R, Kc, chunk)
+    pscore = torch.empty(nchunks, R, dtype=torch.float32, device=dev)
+    pidx = torch.empty(nchunks, R, dtype=torch.int32, device=dev)
+    code = torch.zeros(B, Tmax, dtype=torch.int32, device=dev)
+    merged = torch.zeros(B, Tmax, dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    bad = torch.empty(B, dtype=torch.int32, device=dev)
+    call("mms2ut_kmeans_assign", X.data_ptr(), d, R, d, c_hi.data_ptr(), c_lo.data_ptr(), cnorm.data_ptr(), Kc, chunk,
+         pscore.data_ptr(), pidx.data_ptr(), _s())
+    call("mms2ut_kmeans_fold", pscore.data_ptr(), pidx.data_ptr(), nchunks, B, Tmax, _p(lens), code.data_ptr(),
+         merged.data_ptr(), count.data_ptr(), bad.data_ptr(), _s())
+    return code, merged, count, bad
 
 
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]
