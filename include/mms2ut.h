@@ -319,6 +319,27 @@ int mms2ut_mha_varlen_bwd(const mms2ut_attn_args* args, const mms2ut_half* dout,
                           mms2ut_half* dk, int64_t lddk, int64_t sdkb, mms2ut_half* dv,
                           int64_t lddv, int64_t sdvb, hipStream_t stream);
 
+/* Launch plans: the decisions the two launchers above take for these arguments (the launchers call
+ * the same code), without launching anything.  Same argument checks and errors as the launchers.
+ *   forward:  nw = waves per block (8 or 16; a block owns 16*nw query rows), short_k = 1 when the
+ *             head's whole K / V is staged in LDS up front (Tk <= 128), grid_x * grid_y blocks.
+ *   backward: fused = 1 for the one-launch persistent kernel (nkc = key chunks of 128, 1 or 2;
+ *             kv16 = 16-byte dK / dV stores; grid = blocks, rounds = ceil(B*H / grid) heads per
+ *             block at most), else the three-kernel route (rows_prep = 1: the D = rowsum(dO*O)
+ *             kernel that reads whole token rows, 0: the one-wave-per-(head, row) kernel).
+ *             Fields of the route not taken are 0.                                            */
+typedef struct mms2ut_attn_fwd_plan {
+  int nw, short_k, grid_x, grid_y;
+} mms2ut_attn_fwd_plan;
+typedef struct mms2ut_attn_bwd_plan {
+  int fused, nkc, kv16, rows_prep, grid, rounds;
+} mms2ut_attn_bwd_plan;
+int mms2ut_mha_varlen_fwd_plan(const mms2ut_attn_args* args, mms2ut_attn_fwd_plan* plan);
+int mms2ut_mha_varlen_bwd_plan(const mms2ut_attn_args* args, const mms2ut_half* dout, int64_t lddo,
+                               int64_t sdob, float* Dd, mms2ut_half* dq, int64_t lddq, int64_t sdqb,
+                               mms2ut_half* dk, int64_t lddk, int64_t sdkb, mms2ut_half* dv,
+                               int64_t lddv, int64_t sdvb, mms2ut_attn_bwd_plan* plan);
+
 /* ---------------------------------------------------------------- elementwise / embedding */
 /* y = dropout(x) elementwise (n elements, counter offset) ; y may alias x                   */
 int mms2ut_dropout_fwd(const mms2ut_half* x, mms2ut_half* y, int64_t n, float p, uint64_t seed,

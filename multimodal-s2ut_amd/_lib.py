@@ -72,6 +72,17 @@ class AttnArgs(C.Structure):
 
 ATTN_ARGS = _packer(AttnArgs)
 
+
+class AttnFwdPlan(C.Structure):
+    """mms2ut_attn_fwd_plan: what mms2ut_mha_varlen_fwd would launch."""
+    _fields_ = [(n, i32) for n in ("nw", "short_k", "grid_x", "grid_y")]
+
+
+class AttnBwdPlan(C.Structure):
+    """mms2ut_attn_bwd_plan: what mms2ut_mha_varlen_bwd would launch."""
+    _fields_ = [(n, i32) for n in ("fused", "nkc", "kv16", "rows_prep", "grid", "rounds")]
+
+
 LAYER_ENC, LAYER_DEC = 0, 1
 (SLOT_M1, SLOT_R1, SLOT_H1, SLOT_QKV, SLOT_LSE_SA, SLOT_O, SLOT_XA, SLOT_M2, SLOT_R2, SLOT_H2, SLOT_Q, SLOT_LSE_CA,
  SLOT_CO, SLOT_XB, SLOT_M3, SLOT_R3, SLOT_H3, SLOT_F1, SLOT_OUT, LAYER_NSLOT) = range(20)
@@ -234,6 +245,9 @@ SIGNATURES = {
     "mms2ut_mha_varlen_fwd": (i32, [vp, vp]),   # ATTN_ARGS.pack(...) bytes
     "mms2ut_mha_varlen_bwd": (i32, [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, i64,
                                     vp, i64, i64, vp]),
+    "mms2ut_mha_varlen_fwd_plan": (i32, [vp, vp]),
+    "mms2ut_mha_varlen_bwd_plan": (i32, [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, i64,
+                                         vp, i64, i64, vp]),
     "mms2ut_dropout_fwd": (i32, [vp, vp, i64, f32, u64, u64, vp]),
     "mms2ut_dropout_mask": (i32, [vp, i64, f32, u64, u64, vp]),
     "mms2ut_encoder_embed_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, u64, u64, vp]),

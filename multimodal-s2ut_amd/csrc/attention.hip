@@ -999,24 +999,91 @@ AttnP make_params(const mms2ut_attn_args* a) {
   return P;
 }
 
-}  // namespace
+bool hd_supported(int hd) {
+  return pick_hd(hd, [](auto) { return 0; }) == 0;
+}
 
-extern "C" int mms2ut_mha_varlen_fwd(const mms2ut_attn_args* a, hipStream_t s) {
+// The forward launcher's decisions (argument checks included); launches nothing.
+int plan_fwd(const mms2ut_attn_args* a, AttnP& P, mms2ut_attn_fwd_plan& pl) {
   if (check_common(a)) return 1;
   MMS_REQUIRE(a->lse != nullptr, "attention fwd: lse buffer required");
-  AttnP P = make_params(a);
+  if (!hd_supported(a->hd)) return 1;
+  P = make_params(a);
   // each wave owns 16 query rows: 8 waves (128 rows) for Tq <= 128, else 16 waves (256 rows), so
   // that for every length up to 256 each (b, h) streams its K/V exactly once
-  const int nw = a->Tq > 16 * ATTN_NW ? 2 * ATTN_NW : ATTN_NW;
-  dim3 grid((a->Tq + 16 * nw - 1) / (16 * nw), a->B * a->H);
+  pl.nw = a->Tq > 16 * ATTN_NW ? 2 * ATTN_NW : ATTN_NW;
+  pl.short_k = a->Tk <= 2 * KB && P.ldk < (1L << 24) && P.ldv < (1L << 24);
+  pl.grid_x = (a->Tq + 16 * pl.nw - 1) / (16 * pl.nw);
+  pl.grid_y = a->B * a->H;
+  return 0;
+}
+
+// The backward launcher's decisions (argument checks included); launches nothing.
+int plan_bwd(const mms2ut_attn_args* a, const mms2ut_half* dout, int64_t lddo, int64_t sdob, float* Dd,
+             mms2ut_half* dq, int64_t lddq, int64_t sdqb, mms2ut_half* dk, int64_t lddk, int64_t sdkb,
+             mms2ut_half* dv, int64_t lddv, int64_t sdvb, AttnP& P, mms2ut_attn_bwd_plan& pl) {
+  if (check_common(a)) return 1;
+  MMS_REQUIRE(a->lse && dout && Dd && dq && dk && dv, "attention bwd: null buffers");
+  MMS_REQUIRE(lddo % 8 == 0 && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0, "attention bwd: bad strides");
+  if (!hd_supported(a->hd)) return 1;
+  P = make_params(a);
+  P.dout = dout; P.lddo = lddo; P.sdob = sdob ? sdob : (long)a->Tq * lddo;
+  P.Dd = Dd;
+  P.dq = dq; P.lddq = lddq; P.sdqb = sdqb ? sdqb : (long)a->Tq * lddq;
+  P.dk = dk; P.lddk = lddk; P.sdkb = sdkb ? sdkb : (long)a->Tk * lddk;
+  P.dv = dv; P.lddv = lddv; P.sdvb = sdvb ? sdvb : (long)a->Tk * lddv;
+  P.kv16 = P.lddk % 8 == 0 && P.lddv % 8 == 0 && P.sdkb % 8 == 0 && P.sdvb % 8 == 0 &&
+           (a->hd % 16) == 0 && ((uintptr_t)P.dk & 15) == 0 && ((uintptr_t)P.dv & 15) == 0;
+  pl = mms2ut_attn_bwd_plan{};
+  const int Z = a->B * a->H;
+  pl.fused = a->Tk <= 256 && a->hd <= 96 &&
+             P.ldo % 8 == 0 && P.sob % 8 == 0 && ((uintptr_t)P.o & 15) == 0 &&
+             P.lddo % 8 == 0 && P.sdob % 8 == 0 && ((uintptr_t)P.dout & 15) == 0;
+  if (pl.fused) {
+    // persistent grid: one block per CU (the kernel's LDS allows no second), each looping
+    // over heads so that the next head's loads overlap the current head's MFMA phases
+    pl.grid = std::min(Z, num_cus());
+    pl.rounds = (Z + pl.grid - 1) / pl.grid;
+    pl.nkc = a->Tk <= 128 ? 1 : 2;
+    pl.kv16 = P.kv16;
+  } else {
+    const int HD = a->hd;
+    pl.rows_prep = a->H <= 64 && 64 % a->H == 0 && (HD / 4) % (64 / a->H) == 0 &&
+                   P.ldo % 4 == 0 && P.lddo % 4 == 0 && P.sob % 4 == 0 && P.sdob % 4 == 0 &&
+                   ((uintptr_t)P.o & 7) == 0 && ((uintptr_t)P.dout & 7) == 0;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int mms2ut_mha_varlen_fwd_plan(const mms2ut_attn_args* a, mms2ut_attn_fwd_plan* plan) {
+  MMS_REQUIRE(plan != nullptr, "attention plan: null plan");
+  AttnP P;
+  return plan_fwd(a, P, *plan);
+}
+
+extern "C" int mms2ut_mha_varlen_bwd_plan(const mms2ut_attn_args* a, const mms2ut_half* dout, int64_t lddo,
+                                          int64_t sdob, float* Dd, mms2ut_half* dq, int64_t lddq, int64_t sdqb,
+                                          mms2ut_half* dk, int64_t lddk, int64_t sdkb, mms2ut_half* dv,
+                                          int64_t lddv, int64_t sdvb, mms2ut_attn_bwd_plan* plan) {
+  MMS_REQUIRE(plan != nullptr, "attention plan: null plan");
+  AttnP P;
+  return plan_bwd(a, dout, lddo, sdob, Dd, dq, lddq, sdqb, dk, lddk, sdkb, dv, lddv, sdvb, P, *plan);
+}
+
+extern "C" int mms2ut_mha_varlen_fwd(const mms2ut_attn_args* a, hipStream_t s) {
+  AttnP P;
+  mms2ut_attn_fwd_plan pl;
+  if (plan_fwd(a, P, pl)) return 1;
+  dim3 grid(pl.grid_x, pl.grid_y);
   return pick_hd(a->hd, [&](auto HDc) {
     constexpr int HD = decltype(HDc)::value;
-    const bool short_k = a->Tk <= 2 * KB && P.ldk < (1L << 24) && P.ldv < (1L << 24);
-    if (nw == ATTN_NW) {
-      if (short_k) hipLaunchKernelGGL((attn_fwd_kernel<HD, ATTN_NW, true>), grid, dim3(64 * ATTN_NW), 0, s, P);
+    if (pl.nw == ATTN_NW) {
+      if (pl.short_k) hipLaunchKernelGGL((attn_fwd_kernel<HD, ATTN_NW, true>), grid, dim3(64 * ATTN_NW), 0, s, P);
       else hipLaunchKernelGGL((attn_fwd_kernel<HD, ATTN_NW>), grid, dim3(64 * ATTN_NW), 0, s, P);
     } else {
-      if (short_k) hipLaunchKernelGGL((attn_fwd_kernel<HD, 2 * ATTN_NW, true>), grid, dim3(128 * ATTN_NW), 0, s, P);
+      if (pl.short_k) hipLaunchKernelGGL((attn_fwd_kernel<HD, 2 * ATTN_NW, true>), grid, dim3(128 * ATTN_NW), 0, s, P);
       else hipLaunchKernelGGL((attn_fwd_kernel<HD, 2 * ATTN_NW>), grid, dim3(128 * ATTN_NW), 0, s, P);
     }
     return mms::check_launch("mha_varlen_fwd");
@@ -1027,34 +1094,18 @@ extern "C" int mms2ut_mha_varlen_bwd(const mms2ut_attn_args* a, const mms2ut_hal
                                      int64_t sdob, float* Dd, mms2ut_half* dq, int64_t lddq, int64_t sdqb,
                                      mms2ut_half* dk, int64_t lddk, int64_t sdkb, mms2ut_half* dv,
                                      int64_t lddv, int64_t sdvb, hipStream_t s) {
-  if (check_common(a)) return 1;
-  MMS_REQUIRE(a->lse && dout && Dd && dq && dk && dv, "attention bwd: null buffers");
-  MMS_REQUIRE(lddo % 8 == 0 && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0, "attention bwd: bad strides");
-  AttnP P = make_params(a);
-  P.dout = dout; P.lddo = lddo; P.sdob = sdob ? sdob : (long)a->Tq * lddo;
-  P.Dd = Dd;
-  P.dq = dq; P.lddq = lddq; P.sdqb = sdqb ? sdqb : (long)a->Tq * lddq;
-  P.dk = dk; P.lddk = lddk; P.sdkb = sdkb ? sdkb : (long)a->Tk * lddk;
-  P.dv = dv; P.lddv = lddv; P.sdvb = sdvb ? sdvb : (long)a->Tk * lddv;
-  {
-    P.kv16 = P.lddk % 8 == 0 && P.lddv % 8 == 0 && P.sdkb % 8 == 0 && P.sdvb % 8 == 0 &&
-             (a->hd % 16) == 0 && ((uintptr_t)P.dk & 15) == 0 && ((uintptr_t)P.dv & 15) == 0;
-  }
+  AttnP P;
+  mms2ut_attn_bwd_plan pl;
+  if (plan_bwd(a, dout, lddo, sdob, Dd, dq, lddq, sdqb, dk, lddk, sdkb, dv, lddv, sdvb, P, pl)) return 1;
   const int Z = a->B * a->H;
-  const bool fused_ok = a->Tk <= 256 && a->hd <= 96 &&
-                        P.ldo % 8 == 0 && P.sob % 8 == 0 && ((uintptr_t)P.o & 15) == 0 &&
-                        P.lddo % 8 == 0 && P.sdob % 8 == 0 && ((uintptr_t)P.dout & 15) == 0;
-  if (fused_ok) {
+  if (pl.fused) {
     return pick_hd(a->hd, [&](auto HDc) {
       constexpr int HD = decltype(HDc)::value;
       if constexpr (HD <= 96) {
-        // persistent grid: one block per CU (the kernel's LDS allows no second), each looping
-        // over heads so that the next head's loads overlap the current head's MFMA phases
-        const int grid = std::min(Z, num_cus());
-        if (a->Tk <= 128)
-          hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, 1>), dim3(grid), dim3(512), 0, s, P, Z);
+        if (pl.nkc == 1)
+          hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, 1>), dim3(pl.grid), dim3(512), 0, s, P, Z);
         else
-          hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, 2>), dim3(grid), dim3(512), 0, s, P, Z);
+          hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, 2>), dim3(pl.grid), dim3(512), 0, s, P, Z);
         return mms::check_launch("mha_varlen_bwd_fused");
       } else {
         mms::set_error("unreachable");
@@ -1064,10 +1115,7 @@ extern "C" int mms2ut_mha_varlen_bwd(const mms2ut_attn_args* a, const mms2ut_hal
   }
   return pick_hd(a->hd, [&](auto HDc) {
     constexpr int HD = decltype(HDc)::value;
-    const bool rows_ok = a->H <= 64 && 64 % a->H == 0 && (HD / 4) % (64 / a->H) == 0 &&
-                         P.ldo % 4 == 0 && P.lddo % 4 == 0 && P.sob % 4 == 0 && P.sdob % 4 == 0 &&
-                         ((uintptr_t)P.o & 7) == 0 && ((uintptr_t)P.dout & 7) == 0;
-    if (rows_ok) {
+    if (pl.rows_prep) {
       const long nrows = (long)a->B * a->Tq;
       hipLaunchKernelGGL((attn_bwd_prep_rows_kernel<HD>), dim3((nrows + 3) / 4), dim3(256), 0, s, P, nrows);
     } else {

@@ -1006,7 +1006,11 @@ def _attn_args(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len,
     seed, off = drop if p > 0 else (0, 0)
     return _lib.ATTN_ARGS.pack(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), ldq, ldk, ldv, ldo,
                                sq, sk, sv, so, B, H, Tq, Tk, hd, 0 if key_len is None else key_len.data_ptr(),
-                               int(causal), scale, p, seed, off, lse.data_ptr())
+                               int(causal), scale, p, seed, off, 0 if lse is None else lse.data_ptr())
+
+
+def _plan_dict(plan):
+    return {n: int(getattr(plan, n)) for n, _ in plan._fields_}
 
 
 def mha_fwd(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len=None, causal=False,
@@ -1020,12 +1024,40 @@ def mha_fwd(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len=Non
     return lse
 
 
+def mha_fwd_plan(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len=None, causal=False,
+                 p=0.0, drop=None, sq=0, sk=0, sv=0, so=0):
+    """What mha_fwd would launch for these arguments (mms2ut_mha_varlen_fwd_plan; host only):
+    {nw, short_k, grid_x, grid_y}.  Raises as mha_fwd would on arguments it rejects."""
+    lse = torch.empty(1, dtype=torch.float32, device=q.device)   # only its presence is looked at
+    a = _attn_args(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len, causal, p, drop, lse,
+                   sq, sk, sv, so)
+    plan = _lib.AttnFwdPlan()
+    call("mms2ut_mha_varlen_fwd_plan", a, ctypes.addressof(plan))
+    return _plan_dict(plan)
+
+
 def mha_bwd(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len, causal, p, drop, lse,
-            dout, lddo, dq, lddq, dk, lddk, dv, lddv):
-    a = _attn_args(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len, causal, p, drop, lse)
+            dout, lddo, dq, lddq, dk, lddk, dv, lddv, sq=0, sk=0, sv=0, so=0, sdo=0, sdq=0, sdk=0, sdv=0):
+    """Fused attention backward: dq / dk / dv written.  s*: batch strides in elements as in mha_fwd."""
+    a = _attn_args(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len, causal, p, drop, lse,
+                   sq, sk, sv, so)
     Dd = torch.empty(B * H * Tq, dtype=torch.float32, device=q.device)
-    call("mms2ut_mha_varlen_bwd", a, dout.data_ptr(), int(lddo), 0, Dd.data_ptr(), dq.data_ptr(),
-         int(lddq), 0, dk.data_ptr(), int(lddk), 0, dv.data_ptr(), int(lddv), 0, _s())
+    call("mms2ut_mha_varlen_bwd", a, dout.data_ptr(), int(lddo), int(sdo), Dd.data_ptr(), dq.data_ptr(),
+         int(lddq), int(sdq), dk.data_ptr(), int(lddk), int(sdk), dv.data_ptr(), int(lddv), int(sdv), _s())
+
+
+def mha_bwd_plan(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len, causal, p, drop, lse,
+                 dout, lddo, dq, lddq, dk, lddk, dv, lddv, sq=0, sk=0, sv=0, so=0, sdo=0, sdq=0, sdk=0, sdv=0):
+    """What mha_bwd would launch for these arguments (mms2ut_mha_varlen_bwd_plan; host only):
+    {fused, nkc, kv16, rows_prep, grid, rounds}.  Raises as mha_bwd would on arguments it rejects."""
+    a = _attn_args(q, k, v, o, ldq, ldk, ldv, ldo, B, H, Tq, Tk, hd, scale, key_len, causal, p, drop, lse,
+                   sq, sk, sv, so)
+    plan = _lib.AttnBwdPlan()
+    Dd = torch.empty(1, dtype=torch.float32, device=q.device)    # only its presence is looked at
+    call("mms2ut_mha_varlen_bwd_plan", a, dout.data_ptr(), int(lddo), int(sdo), Dd.data_ptr(), dq.data_ptr(),
+         int(lddq), int(sdq), dk.data_ptr(), int(lddk), int(sdk), dv.data_ptr(), int(lddv), int(sdv),
+         ctypes.addressof(plan))
+    return _plan_dict(plan)
 
 # ============================================================================ elementwise
 
