@@ -793,6 +793,40 @@ int mms2ut_kmeans_assign(const void* X, int64_t ldx, int R, int d, const void* c
 int mms2ut_kmeans_fold(const float* pscore, const int32_t* pidx, int nchunks, int B, int Tmax, const int32_t* lens,
                        int32_t* code, int32_t* merged, int32_t* count, int32_t* bad, hipStream_t stream);
 
+/* ---------------------------------------------------------------- image front end (ViT features)
+ * timm's eval transform of the vit_*_patch16_384 models on the device: torchvision Resize(S, bicubic) on
+ * a PIL image, CenterCrop(S), ToTensor, Normalize, then the patch rows of the patch-embedding GEMM; one
+ * launch for the batch.  The resample is Pillow's 8-bit Image.resize(BICUBIC) bit for bit: a horizontal
+ * then a vertical pass with int32 coefficients of 22 fractional bits, each pixel
+ * clamp((2^21 + sum pix * k) >> 22, 0, 255), the intermediate kept as uint8 (in LDS).
+ *   img: the decoded images, packed uint8 HWC (row stride 3 w), image b at byte offset desc[b].src.
+ *   tab: int32 tables the host computed in double (vision.py resample_rows), for the cropped S x S
+ *     window only.  Per axis of image b: S pairs (first source index, taps) at tab + hb / vb, and S rows
+ *     of hn / vn coefficients (taps <= hn used) at tab + hk / vk.  An axis that is not resampled is the
+ *     table (i, 1), coefficient 2^22.
+ *   norm: fp16 [3][256], the normalised value of every uint8 per channel ((u8 / 255 - mean) / std in
+ *     fp32, rounded once).
+ *   out: fp16 [B, (S/P)^2, 3 P P], a patch's columns in (c, py, px) order.
+ *   max_rows: the most source rows any patch row of the batch reads; max_rows * P * 3 bytes of LDS,
+ *     at most MMS_VISION_TILE_BYTES.
+ * A descriptor or table offset that does not fit img_bytes / tab_len (int32s) leaves that image's
+ * patches unwritten; nothing is read or written out of bounds.                                      */
+#define MMS_VISION_TILE_BYTES 49152
+#define MMS_VISION_MAX_SIDE   65535
+typedef struct mms2ut_image_desc {
+  int64_t src;            /* byte offset of pixel (0, 0) in img                                    */
+  int32_t w, h;           /* source width and height                                               */
+  int32_t hb, hk, hn;     /* horizontal: bounds offset, coefficient offset, coefficients per row   */
+  int32_t vb, vk, vn;     /* vertical: the same                                                    */
+} mms2ut_image_desc;
+int mms2ut_vision_patches(const uint8_t* img, int64_t img_bytes, const mms2ut_image_desc* desc, int B,
+                          const int32_t* tab, int64_t tab_len, const mms2ut_half* norm, mms2ut_half* out,
+                          int S, int P, int max_rows, hipStream_t stream);
+/* bad[b] = 1 where x[b * ld .. b * ld + n) holds an fp16 inf or NaN; other entries are left as they
+ * are (the caller zeroes bad).  x 16-byte aligned, ld and n multiples of 8.                          */
+int mms2ut_nonfinite_rows_f16(const mms2ut_half* x, int64_t ld, int B, int64_t n, int32_t* bad,
+                              hipStream_t stream);
+
 /* ---------------------------------------------------------------- transformer layers
  * One whole pre-LN transformer layer per call — SURVEY §8b "encoder / decoder layer fwd/bwd":
  *   MMS_LAYER_ENC: fairseq TransformerEncoderLayer (encoder_normalize_before; A5, reached from

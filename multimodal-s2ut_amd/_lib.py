@@ -187,6 +187,15 @@ class AsrConvArgs(C.Structure):
 ASR_CONV_ARGS = _packer(AsrConvArgs)
 HUBERT_GN_PARTS, KMEANS_LO_SCALE = 256, 2048              # include/mms2ut.h MMS_HUBERT_GN_PARTS, MMS_KMEANS_LO_SCALE
 
+VISION_TILE_BYTES, VISION_MAX_SIDE = 49152, 65535         # include/mms2ut.h MMS_VISION_*
+
+
+class ImageDesc(C.Structure):
+    """mms2ut_image_desc (include/mms2ut.h): one image of a mms2ut_vision_patches launch."""
+    _fields_ = [("src", i64), ("w", C.c_int32), ("h", C.c_int32)] + \
+        [(n, C.c_int32) for n in ("hb", "hk", "hn", "vb", "vk", "vn")]
+
+
 # name -> (restype, argtypes); every symbol include/mms2ut.h declares
 SIGNATURES = {
     "mms2ut_last_error": (C.c_char_p, []),
@@ -297,6 +306,8 @@ SIGNATURES = {
     "mms2ut_kmeans_chunks": (i32, [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mms2ut_kmeans_assign": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "mms2ut_kmeans_fold": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "mms2ut_vision_patches": (i32, [vp, i64, vp, i32, vp, i64, vp, vp, i32, i32, i32, vp]),
+    "mms2ut_nonfinite_rows_f16": (i32, [vp, i64, i32, i64, vp, vp]),
     "mms2ut_layer_arena": (i32, [vp, vp, vp]),
     "mms2ut_layer_scratch": (i32, [vp, f32, vp, vp]),
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),

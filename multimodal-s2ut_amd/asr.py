@@ -179,6 +179,27 @@ def greedy_decode(ids, id_to_token, blank, delimiter="|", cleanup=True, lower=Fa
     return tokens_to_text(collapse(ids, blank), id_to_token, delimiter, cleanup, lower)
 
 
+def prenorm_layers(Hb, layers, H, eps, lens32=None):
+    """Pre-LN transformer layers (packed q|k|v with bias, erf-GELU MLP, both residuals in the GEMM
+    epilogue) over fp16 [B, Tmax, d] -> fp16 [B * Tmax, d].  layers: dicts of ln1_g ln1_b wqkv bqkv wo bo
+    ln2_g ln2_b w1 b1 w2 b2.  Shared by the wav2vec2 encoder here and the ViT blocks of vision.py."""
+    B, Tm, d = Hb.shape
+    R, hd = B * Tm, d // H
+    X = Hb.reshape(R, d)
+    for L in layers:
+        y = K.layernorm(X, L["ln1_g"], L["ln1_b"], eps)[0]
+        qkv = K.linear(y, L["wqkv"], L["bqkv"])
+        o = torch.empty(R, d, dtype=K.F16, device=X.device)
+        K.mha_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], o, 3 * d, 3 * d, 3 * d, d, B, H, Tm, Tm, hd, hd ** -0.5,
+                  key_len=lens32)
+        X = K.linear(o, L["wo"], L["bo"], epi=K.EPI_DROP_RESID, aux=X)
+        y = K.layernorm(X, L["ln2_g"], L["ln2_b"], eps)[0]
+        z = torch.empty(R, L["w1"].shape[0], dtype=K.F16, device=X.device)
+        f = K.linear(y, L["w1"], L["b1"], epi=K.EPI_GELU_DROP, out2=z)
+        X = K.linear(f, L["w2"], L["b2"], epi=K.EPI_DROP_RESID, aux=X)
+    return X
+
+
 class _ConvLayer:
     __slots__ = ("w", "b", "g", "be", "cout", "k", "stride")
 
@@ -318,21 +339,7 @@ class Wav2Vec2CTC:
 
     def layers_forward(self, Hb, lens32=None):
         """The stable-LN transformer layers over fp16 [B, Tmax, d] -> fp16 [B * Tmax, d]."""
-        B, Tm, d = Hb.shape
-        R, eps = B * Tm, self.eps
-        X = Hb.reshape(R, d)
-        for L in self.layers:
-            y = K.layernorm(X, L["ln1_g"], L["ln1_b"], eps)[0]
-            qkv = K.linear(y, L["wqkv"], L["bqkv"])
-            o = torch.empty(R, d, dtype=K.F16, device=X.device)
-            K.mha_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], o, 3 * d, 3 * d, 3 * d, d, B, self.H, Tm, Tm, self.hd,
-                      self.hd ** -0.5, key_len=lens32)
-            X = K.linear(o, L["wo"], L["bo"], epi=K.EPI_DROP_RESID, aux=X)
-            y = K.layernorm(X, L["ln2_g"], L["ln2_b"], eps)[0]
-            z = torch.empty(R, L["w1"].shape[0], dtype=K.F16, device=X.device)
-            f = K.linear(y, L["w1"], L["b1"], epi=K.EPI_GELU_DROP, out2=z)
-            X = K.linear(f, L["w2"], L["b2"], epi=K.EPI_DROP_RESID, aux=X)
-        return X
+        return prenorm_layers(Hb, self.layers, self.H, self.eps, lens32)
 
     def head(self, X, B, Tm):
         """encoder.layer_norm and lm_head (bias left to ctc_greedy): fp16 [B * Tmax, d] -> fp32 [B, Tmax, Vp]."""

@@ -1776,4 +1776,63 @@ def kmeans_assign(X, c_hi, c_lo, cnorm, lens=None, *, chunk=None):
     return code, merged, count, bad
 
 
+# ============================================================================ image front end (ViT features)
+
+VISION_TILE_BYTES, VISION_MAX_SIDE = _lib.VISION_TILE_BYTES, _lib.VISION_MAX_SIDE
+
+
+def vision_patches(img, desc, tab, norm, S, P, max_rows, out=None):
+    """The image front end, one launch: Pillow's 8-bit bicubic resample, centre crop, normalisation and
+    patchify of a batch (csrc/vision.hip).  img uint8 [bytes] and tab int32 [n] on the device; desc: the
+    batch's descriptors on the host, a numpy array of the mms2ut_image_desc layout (np.dtype(_lib.ImageDesc)),
+    checked here against both buffers and then uploaded; norm fp16 [3, 256].  -> fp16 [B, (S/P)^2, 3 P P]."""
+    import numpy as np
+    _chk(img, torch.uint8)
+    _chk(tab, torch.int32)
+    _chk(norm)
+    dt = np.dtype(_lib.ImageDesc)
+    if desc.dtype != dt or desc.ndim != 1:
+        raise ValueError(f"vision_patches: desc must be a 1-d array of {dt}")
+    B = desc.shape[0]
+    if P < 1 or S < P or S % P:
+        raise ValueError(f"vision_patches: the patch size {P} must divide the image size {S}")
+    if not 1 <= max_rows <= VISION_TILE_BYTES // (3 * P):
+        raise ValueError(f"vision_patches: a tile of {max_rows} source rows x {P} columns exceeds the "
+                         f"{VISION_TILE_BYTES} bytes of LDS a patch may use (the image is reduced too far)")
+    if tuple(norm.shape) != (3, 256) or not (norm.is_contiguous() and img.is_contiguous() and tab.is_contiguous()) \
+            or img.dim() != 1 or tab.dim() != 1:
+        raise ValueError("vision_patches: contiguous img [bytes], tab [n] and norm [3, 256] expected")
+    nb, nt = img.numel(), tab.numel()
+    for d in desc.tolist():
+        src, w, h, hb, hk, hn, vb, vk, vn = d
+        if not (1 <= w <= VISION_MAX_SIDE and 1 <= h <= VISION_MAX_SIDE and 0 <= src and src + 3 * w * h <= nb):
+            raise ValueError(f"vision_patches: image {w}x{h} at byte {src} does not fit the buffer of {nb} bytes")
+        for b, k, n in ((hb, hk, hn), (vb, vk, vn)):
+            if not (n >= 1 and b >= 0 and k >= 0 and b + 2 * S <= nt and k + S * n <= nt):
+                raise ValueError(f"vision_patches: table offsets ({b}, {k}, stride {n}) outside the table of {nt}")
+    npatch = (S // P) ** 2
+    if out is None:
+        out = torch.empty(B, npatch, 3 * P * P, dtype=F16, device=img.device)
+    _chk(out)
+    assert out.is_contiguous() and out.numel() == B * npatch * 3 * P * P
+    if B == 0:
+        return out
+    ddev = torch.from_numpy(desc.view(np.uint8)).to(img.device)
+    call("mms2ut_vision_patches", img.data_ptr(), nb, ddev.data_ptr(), B, tab.data_ptr(), nt, norm.data_ptr(),
+         out.data_ptr(), int(S), int(P), int(max_rows), _s())
+    return out
+
+
+def nonfinite_rows(x):
+    """int32 [B]: 1 where row b of contiguous fp16 x [B, ...] holds an inf or a NaN."""
+    _chk(x)
+    B = x.shape[0]
+    n = x.numel() // max(B, 1)
+    if not x.is_contiguous() or n % 8:
+        raise ValueError(f"nonfinite_rows: contiguous rows of a multiple of 8 elements expected, got {tuple(x.shape)}")
+    bad = torch.zeros(B, dtype=torch.int32, device=x.device)
+    call("mms2ut_nonfinite_rows_f16", x.data_ptr(), n, B, n, bad.data_ptr(), _s())
+    return bad
+
+
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]
