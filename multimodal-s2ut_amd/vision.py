@@ -7,7 +7,8 @@ image, CenterCrop(S), ToTensor, Normalize(mean = std = 0.5) -- runs on the devic
 (csrc/vision.hip): Pillow's 8-bit bicubic resample bit for bit from coefficient tables computed here in
 double, the crop, the normalisation as a table lookup, and the patch rows.  The patch embedding is one
 batched NT GEMM whose epilogue adds pos_embed[1:] and writes at token offset 1 (the class rows are one
-strided copy); the blocks are asr.prenorm_layers, the layer loop of the wav2vec2 encoder, at eps 1e-6.
+strided copy); the blocks are encoders.transformer_layers, the pre-LN layer loop the wav2vec2 encoder runs,
+at eps 1e-6.  The checked getter and the layer dictionary are encoders.py's too.
 
 ``timm``, ``torchvision`` and ``transformers`` are not dependencies: the semantics are restated here and
 in tests/vit_ref.py; the checkpoint's key names and tensor shapes pin the loader."""
@@ -21,7 +22,7 @@ import torch
 
 from . import _lib
 from . import kernels as K
-from .asr import prenorm_layers, read_safetensors
+from .encoders import TIMM_LAYER, Weights, layer_dict, read_safetensors, transformer_layers
 
 LN_EPS = 1e-6                   # timm's VisionTransformer: partial(nn.LayerNorm, eps=1e-6)
 PRECISION_BITS = 22             # Pillow's 8-bit resample: 32 - 8 - 2
@@ -141,36 +142,15 @@ class ViTFeatures:
         self.d, self.H, self.S, self.P = d, H, S, P
         self.npatch = (S // P) ** 2
         self.T = T = self.npatch + 1
-        sd = state_dict
-
-        def get(name, shape):
-            # the kernels trust these shapes: the GEMMs are sized by them
-            if name not in sd:
-                raise KeyError(f"ViT checkpoint: '{name}' is missing")
-            t = sd[name]
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{name} has shape {tuple(t.shape)}, the model implies {tuple(shape)}" +
-                                 (" (position embeddings are not interpolated to other image sizes)"
-                                  if name == "pos_embed" else ""))
-            return t.float()
-
-        f16 = lambda t: t.half().contiguous().to(dev)
+        w = Weights(state_dict, "ViT checkpoint", device,
+                    hints={"pos_embed": " (position embeddings are not interpolated to other image sizes)"})
+        get, f16 = w.get, w.f16
         self.patch_w = f16(get("patch_embed.proj.weight", (d, 3, P, P)).reshape(d, 3 * P * P))
         self.patch_b = f16(get("patch_embed.proj.bias", (d,)))
         pos, cls = get("pos_embed", (1, T, d))[0], get("cls_token", (1, 1, d))[0, 0]
         self.row0 = f16((cls + pos[0]).reshape(1, d))            # the class token's row, rounded once
         self.pos = f16(pos[1:])
-        self.layers = []
-        for l in range(c["layers"]):
-            p = f"blocks.{l}."
-            self.layers.append({
-                "ln1_g": f16(get(p + "norm1.weight", (d,))), "ln1_b": f16(get(p + "norm1.bias", (d,))),
-                "wqkv": f16(get(p + "attn.qkv.weight", (3 * d, d))), "bqkv": f16(get(p + "attn.qkv.bias", (3 * d,))),
-                "wo": f16(get(p + "attn.proj.weight", (d, d))), "bo": f16(get(p + "attn.proj.bias", (d,))),
-                "ln2_g": f16(get(p + "norm2.weight", (d,))), "ln2_b": f16(get(p + "norm2.bias", (d,))),
-                "w1": f16(get(p + "mlp.fc1.weight", (Fd, d))), "b1": f16(get(p + "mlp.fc1.bias", (Fd,))),
-                "w2": f16(get(p + "mlp.fc2.weight", (d, Fd))), "b2": f16(get(p + "mlp.fc2.bias", (d,))),
-            })
+        self.layers = [layer_dict(w, f"blocks.{l}.", d, Fd, TIMM_LAYER) for l in range(c["layers"])]
         self.norm_g, self.norm_b = f16(get("norm.weight", (d,))), f16(get("norm.bias", (d,)))
         self.norm_tab = norm_table(mean, std).contiguous().to(dev)
         self._tab_off, self._tab_host, self._tab_len, self._tab_dev = {}, [], 0, None
@@ -251,7 +231,7 @@ class ViTFeatures:
     def tokens(self, X):
         """fp16 [B, T, d] -> fp16 [B, T, d]: the blocks and the final norm."""
         B, T, d = X.shape
-        Y = prenorm_layers(X, self.layers, self.H, LN_EPS)
+        Y = transformer_layers(X, self.layers, self.H, LN_EPS)
         return K.layernorm(Y, self.norm_g, self.norm_b, LN_EPS)[0].view(B, T, d)
 
     def forward_device(self, images):

@@ -130,7 +130,7 @@ def main(argv=None):
 
         def feats():
             for b in range(B):
-                m.features(xs[b], out=Hb[b])
+                m.utterance(xs[b], out=Hb[b])
 
         report(f"{B} utts: extractor + projection + positional conv", timed(feats, w, r))
         XB = m.layers_forward(Hb, lens32)

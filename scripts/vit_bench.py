@@ -93,9 +93,9 @@ def main(argv=None):
         P = m.patches(ims)
         row("patch embed + assembly", t := timed(lambda: m.embed(P), w, r), f", {B * fl[2] / t[0] / 1e9:.1f} TF/s")
         X = m.embed(P)
-        row("layers", t := timed(lambda: V.prenorm_layers(X, m.layers, m.H, V.LN_EPS), w, r),
+        row("layers", t := timed(lambda: V.transformer_layers(X, m.layers, m.H, V.LN_EPS), w, r),
             f", {B * (fl[0] + fl[1]) / t[0] / 1e9:.1f} TF/s = {B * (fl[0] + fl[1]) / t[0] / 1e9 / PEAK_TF:.3f} of peak")
-        Y = V.prenorm_layers(X, m.layers, m.H, V.LN_EPS)
+        Y = V.transformer_layers(X, m.layers, m.H, V.LN_EPS)
         host = torch.empty(B, m.T, m.d, dtype=K.F16, pin_memory=True)
 
         def tail():
