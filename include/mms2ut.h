@@ -522,6 +522,25 @@ int mms2ut_splitk_epilogue_ln_f16(const float* slabs, int nsplit, int64_t slab, 
 int mms2ut_beam_topk(const float* lprobs, const float* prev_scores, int64_t ld_prev, int bsz, int beam, int V,
                      int first_step, int k, float* out_score, int64_t* out_tok, int64_t* out_beam,
                      uint64_t* work, hipStream_t stream);
+/* The search bookkeeping around BeamSearch.step (SequenceGenerator._generate); bool tensors are
+ * bytes 0/1.  beam_eos_scan: eos_mask [bsz][k] = (cand_tok == eos_idx && cand_score != -inf),
+ * cleared where j < beam and ignore [bsz][beam] is set; *count (device int32) = the true entries
+ * in columns [0, beam): the hypotheses that finish at this step.  Needs 1 <= beam <= k.        */
+int mms2ut_beam_eos_scan(const float* cand_score, const int64_t* cand_tok, const uint8_t* ignore, int bsz,
+                         int beam, int k, int eos_idx, uint8_t* eos_mask, int32_t* count, hipStream_t stream);
+/* beam_advance: per sentence b, candidate j is masked when eos_mask[b][j] or (j < beam and
+ * ignore[b][j]); the beam smallest of masked*2*beam + j, ascending (torch.topk largest=False),
+ * become hypotheses r = 0 .. beam-1: active [bsz*beam] = b*beam + cand_beam[b][j] (the parent
+ * row, fairseq's reorder_state), new_ignore [bsz][beam] = masked,
+ * tok_out[b*beam+r][0..step] = tok_in[parent][0..step], tok_out[..][step+1] = cand_tok[b][j],
+ * score_out[b*beam+r][0..step-1] = score_in[parent][0..step-1], score_out[..][step] = cand_score[b][j].
+ * Histories are [bsz*beam][ldt] int64 / [bsz*beam][lds] fp32 with step + 2 <= ldt, step + 1 <= lds;
+ * the update is out of place (children may share a parent): *_out must differ from *_in, and
+ * columns past the ones named are left as they are.  1 <= beam <= k <= 32, cand_beam in [0, beam). */
+int mms2ut_beam_advance(const uint8_t* eos_mask, const uint8_t* ignore, const float* cand_score,
+                        const int64_t* cand_tok, const int64_t* cand_beam, int bsz, int beam, int k, int step,
+                        const int64_t* tok_in, int64_t* tok_out, int64_t ldt, const float* score_in,
+                        float* score_out, int64_t lds, uint8_t* new_ignore, int64_t* active, hipStream_t stream);
 /* reorder_incremental_state: src [L][Nsrc][maxT][width], dst [L][N][maxT][width] (each decoder
  * layer's self-attention K|V rows); dst[l][n][0:rows] = src[l][idx[n]][0:rows], idx[n] < Nsrc.
  * width % 8 == 0, 16-B aligned.                                                              */

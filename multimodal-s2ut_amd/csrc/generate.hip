@@ -377,7 +377,128 @@ __global__ void __launch_bounds__(64) beam_topk_merge_kernel(const uint64_t* __r
   }
 }
 
+// SequenceGenerator._generate's bookkeeping around BeamSearch.step (the candidates come from
+// beam_topk above): two launches instead of ~twenty small torch ones.  Bool tensors are bytes 0/1.
+//   * beam_eos_scan: eos_mask[b][j] = tok == eos && score != -inf, cleared where j < beam and
+//     candidate j is ignored (its hypothesis ended at an earlier step); *count = the true entries
+//     with j < beam — the hypotheses that finish at this step, the one number the host reads.
+//     One block over all bsz*k candidates (a few thousand at most), integer sum: no atomics.
+__global__ void __launch_bounds__(256) beam_eos_scan_kernel(const float* __restrict__ score,
+                                                            const int64_t* __restrict__ tok,
+                                                            const uint8_t* __restrict__ ignore, int bsz, int beam,
+                                                            int k, int eos, uint8_t* __restrict__ mask,
+                                                            int* __restrict__ count) {
+  __shared__ int s_cnt[4];
+  const int n = bsz * k;
+  int c = 0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int b = i / k, j = i - b * k;
+    bool m = tok[i] == (int64_t)eos && score[i] != -INFINITY;
+    if (j < beam) {
+      m = m && !ignore[b * beam + j];
+      c += m;
+    }
+    mask[i] = m;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) *count = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
+
+//   * beam_advance: the active-hypothesis selection and the history update.  One block per
+//     sentence.  Wave 0: candidate j (< k <= 32, one per lane) is masked when it is </s> or
+//     (j < beam) ignored; the `beam` smallest of masked*cand_size + j are the unmasked candidates
+//     in order, then the masked ones in order, so a candidate's rank is a prefix count of two
+//     ballots (torch.topk(largest=False) over distinct keys).  Rank r < beam becomes hypothesis r
+//     of the sentence: parent row b*beam + cand_beam, new ignore flag = masked.  Then one wave per
+//     new hypothesis copies the parent's token / score history from the *_in buffers to the *_out
+//     buffers (two children may share a parent and rows permute, so the update is out of place:
+//     the caller swaps the buffers every step) and appends the candidate's token and score.
+__global__ void __launch_bounds__(256) beam_advance_kernel(const uint8_t* __restrict__ eos_mask,
+                                                           const uint8_t* __restrict__ ignore,
+                                                           const float* __restrict__ cand_score,
+                                                           const int64_t* __restrict__ cand_tok,
+                                                           const int64_t* __restrict__ cand_beam, int beam, int k,
+                                                           int step, const int64_t* __restrict__ tok_in,
+                                                           int64_t* __restrict__ tok_out, long ldt,
+                                                           const float* __restrict__ sc_in,
+                                                           float* __restrict__ sc_out, long lds,
+                                                           uint8_t* __restrict__ new_ignore,
+                                                           int64_t* __restrict__ active) {
+  __shared__ int s_parent[32];
+  __shared__ int64_t s_tok[32];
+  __shared__ float s_score[32];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.x;
+  if (w == 0) {
+    const bool in = lane < k;
+    bool m = false;
+    int64_t tk = 0, bm = 0;
+    float sc = 0.f;
+    if (in) {
+      m = eos_mask[(long)b * k + lane] != 0;
+      if (lane < beam) m = m || ignore[(long)b * beam + lane] != 0;
+      tk = cand_tok[(long)b * k + lane];
+      bm = cand_beam[(long)b * k + lane];
+      sc = cand_score[(long)b * k + lane];
+    }
+    const uint64_t live = __ballot(in && !m), dead = __ballot(in && m);
+    const uint64_t below = (1ull << lane) - 1ull;
+    const int rank = m ? __popcll(live) + __popcll(dead & below) : __popcll(live & below);
+    if (in && rank < beam) {
+      const int parent = b * beam + (int)bm;
+      s_parent[rank] = parent;
+      s_tok[rank] = tk;
+      s_score[rank] = sc;
+      new_ignore[(long)b * beam + rank] = m;
+      active[(long)b * beam + rank] = parent;
+    }
+  }
+  __syncthreads();
+  for (int r = w; r < beam; r += 4) {
+    const long src = s_parent[r], dst = (long)b * beam + r;
+    const int64_t* ti = tok_in + src * ldt;
+    int64_t* to = tok_out + dst * ldt;
+    for (int c = lane; c <= step; c += 64) to[c] = ti[c];
+    const float* si = sc_in + src * lds;
+    float* so = sc_out + dst * lds;
+    for (int c = lane; c < step; c += 64) so[c] = si[c];
+    if (lane == 0) {
+      to[step + 1] = s_tok[r];
+      so[step] = s_score[r];
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int mms2ut_beam_eos_scan(const float* cand_score, const int64_t* cand_tok, const uint8_t* ignore, int bsz,
+                                    int beam, int k, int eos_idx, uint8_t* eos_mask, int32_t* count,
+                                    hipStream_t s) {
+  MMS_REQUIRE(bsz >= 0 && beam >= 1 && k >= beam, "beam_eos_scan: need bsz >= 0 and 1 <= beam <= k");
+  MMS_REQUIRE((long)bsz * k < 0x7FFFFFFFL, "beam_eos_scan: bsz * k too large");
+  hipLaunchKernelGGL(beam_eos_scan_kernel, dim3(1), dim3(256), 0, s, cand_score, cand_tok, ignore, bsz, beam, k,
+                     eos_idx, eos_mask, count);
+  return mms::check_launch("beam_eos_scan");
+}
+
+extern "C" int mms2ut_beam_advance(const uint8_t* eos_mask, const uint8_t* ignore, const float* cand_score,
+                                   const int64_t* cand_tok, const int64_t* cand_beam, int bsz, int beam, int k,
+                                   int step, const int64_t* tok_in, int64_t* tok_out, int64_t ldt,
+                                   const float* score_in, float* score_out, int64_t lds, uint8_t* new_ignore,
+                                   int64_t* active, hipStream_t s) {
+  MMS_REQUIRE(beam >= 1 && beam <= k && k <= 32, "beam_advance: need 1 <= beam <= k <= 32");
+  MMS_REQUIRE(step >= 0 && (long)step + 2 <= ldt && (long)step + 1 <= lds,
+              "beam_advance: history rows too short for step (need step + 2 <= ldt, step + 1 <= lds)");
+  MMS_REQUIRE(tok_in != tok_out && score_in != score_out, "beam_advance: the history update is out of place");
+  MMS_REQUIRE((long)bsz * beam < 0x7FFFFFFFL, "beam_advance: bsz * beam too large");
+  if (bsz <= 0) return 0;
+  hipLaunchKernelGGL(beam_advance_kernel, dim3(bsz), dim3(256), 0, s, eos_mask, ignore, cand_score, cand_tok,
+                     cand_beam, beam, k, step, tok_in, tok_out, (long)ldt, score_in, score_out, (long)lds,
+                     new_ignore, active);
+  return mms::check_launch("beam_advance");
+}
 
 extern "C" int mms2ut_log_softmax_step(const h16* logits, int64_t ld, int64_t rows, int V, int pad_idx,
                                        int eos_idx, int mode, float* lprobs, hipStream_t s) {

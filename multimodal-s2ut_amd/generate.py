@@ -21,9 +21,12 @@ Two parts:
   step's pad / eos masking).
 * ``SequenceGenerator`` — fairseq ``SequenceGenerator._generate`` + ``BeamSearch.step`` +
   ``finalize_hypos`` (normalize_scores, len_penalty, min_len 1, no unk penalty / n-gram blocking /
-  prefix / constraints), as device tensor bookkeeping in torch around the decoder above.  Works with
-  any decoder object exposing ``step(tokens_last, step, mode)`` / ``reorder(state, batch_idxs)``
-  (the CPU tests drive it with a toy decoder against oracle/ref_generate.py).
+  prefix / constraints), as device tensor bookkeeping around the decoder above: candidate selection
+  (``beam_topk``) and the per-step bookkeeping (``beam_eos_scan``, ``beam_advance``) are HIP kernels
+  when the decoder exposes them, torch (``TorchBookkeeping``) otherwise; finalisation and the removal
+  of finished sentences are torch.  Works with any decoder object exposing
+  ``step(tokens_last, step, mode)`` / ``reorder(state, batch_idxs)`` (the CPU tests drive it with a
+  toy decoder against oracle/ref_generate.py).
 """
 import math
 import os
@@ -34,6 +37,13 @@ from . import kernels as K
 from .kernels import F16
 
 MODE_NONE, MODE_FORCE_EOS, MODE_NO_EOS = 0, 1, 2
+_CAPTURES = [0]
+
+
+def graph_captures():
+    """How many times a decoder step has been captured as a HIP graph in this process (once per
+    batch, and again each time finished sentences shrink the batch)."""
+    return _CAPTURES[0]
 
 
 def _lin(x, W, b, *, aux=None, relu=False, out=None):
@@ -165,6 +175,16 @@ class IncrementalDecoder:
     def beam_topk(self, lprobs, prev_col, bsz, beam, V, k, first_step):
         return K.beam_topk(lprobs, prev_col, bsz, beam, V, k, first_step)
 
+    # the search bookkeeping of one step as two HIP launches (TorchBookkeeping is the torch form)
+    def beam_eos_scan(self, cand_scores, cand_indices, cands_to_ignore, eos):
+        return K.beam_eos_scan(cand_scores, cand_indices, cands_to_ignore, eos)
+
+    def beam_advance(self, eos_mask, cands_to_ignore, cand_scores, cand_indices, cand_beams, tokens, scores, step,
+                     spare):
+        new_ignore, active = K.beam_advance(eos_mask, cands_to_ignore, cand_scores, cand_indices, cand_beams,
+                                            tokens, scores, step, spare[0], spare[1])
+        return new_ignore, active, spare[0], spare[1]
+
     def step(self, tokens_last, step, mode=MODE_NONE):
         """tokens_last [N] int64 (the token at position `step` of every hypothesis) -> lprobs [N, V]."""
         assert self.step_no == step and self.slot.shape[0] == self.N and step + 1 < self.maxT
@@ -177,12 +197,53 @@ class IncrementalDecoder:
             with torch.cuda.graph(g):
                 self._body()
             self.graph = g
+            _CAPTURES[0] += 1
             g.replay()
         else:
             self._body()
             self.eager_steps += 1
         self.step_no += 1
         return K.log_softmax_step(self.logits, self.V, self.pad, self.eos, mode)
+
+
+class TorchBookkeeping:
+    """One search step's bookkeeping around BeamSearch.step in torch (fairseq's own lines): what
+    ``SequenceGenerator`` runs for a decoder without ``beam_eos_scan`` / ``beam_advance`` (the CPU
+    tests' toy decoder) or when k is outside [beam, 32], and the reference those kernels are tested
+    against."""
+
+    def __init__(self, bsz, beam, device):
+        self.beam, self.cand_size = beam, 2 * beam
+        self.bbsz_offsets = (torch.arange(bsz, device=device) * beam).unsqueeze(1)
+        self.cand_offsets = torch.arange(self.cand_size, device=device)
+
+    def beam_eos_scan(self, cand_scores, cand_indices, cands_to_ignore, eos):
+        """-> (eos_mask [bsz,k], the number of hypotheses that end at this step)."""
+        beam = self.beam
+        eos_mask = cand_indices.eq(eos) & cand_scores.ne(-math.inf)
+        eos_mask[:, :beam][cands_to_ignore] = False
+        return eos_mask, eos_mask[:, :beam].sum()
+
+    def beam_advance(self, eos_mask, cands_to_ignore, cand_scores, cand_indices, cand_beams, tokens, scores, step,
+                     spare=None):
+        """-> (cands_to_ignore, active_bbsz_idx, tokens, scores): the active hypotheses of every
+        sentence and their histories, updated in place (``spare`` is unused)."""
+        beam, cand_size = self.beam, self.cand_size
+        bsz = cand_beams.shape[0]
+        cand_bbsz_idx = cand_beams.add(self.bbsz_offsets[:bsz])
+        eos_mask[:, :beam] = ~((~cands_to_ignore) & (~eos_mask[:, :beam]))
+        active_mask = torch.add(eos_mask.type_as(self.cand_offsets) * cand_size,
+                                self.cand_offsets[: eos_mask.size(1)])
+        new_ignore, active_hypos = torch.topk(active_mask, k=beam, dim=1, largest=False)
+        cands_to_ignore = new_ignore.ge(cand_size)[:, :beam]
+        active_bbsz_idx = torch.gather(cand_bbsz_idx, 1, active_hypos).view(-1)
+        active_scores = torch.gather(cand_scores, 1, active_hypos)
+        tokens[:, : step + 1] = torch.index_select(tokens[:, : step + 1], 0, active_bbsz_idx)
+        tokens.view(bsz, beam, -1)[:, :, step + 1] = torch.gather(cand_indices, 1, active_hypos)
+        if step > 0:
+            scores[:, :step] = torch.index_select(scores[:, :step], 0, active_bbsz_idx)
+        scores.view(bsz, beam, -1)[:, :, step] = active_scores
+        return cands_to_ignore, active_bbsz_idx, tokens, scores
 
 
 class SequenceGenerator:
@@ -211,7 +272,9 @@ class SequenceGenerator:
         num_remaining = bsz
         cand_size = 2 * beam
         bbsz_offsets = (torch.arange(bsz, device=device) * beam).unsqueeze(1)
-        cand_offsets = torch.arange(cand_size, device=device)
+        torch_bk = TorchBookkeeping(bsz, beam, device)
+        hip_bk = decoder if hasattr(decoder, "beam_advance") and hasattr(decoder, "beam_eos_scan") else None
+        spare = None                              # the second tokens / scores pair of the HIP update
         reorder_state, batch_idxs = None, None
         for step in range(max_len + 1):
             if reorder_state is not None:
@@ -235,12 +298,14 @@ class SequenceGenerator:
                 cand_scores, idx = torch.topk(lp.view(bsz, -1), k=k)
                 cand_beams = torch.div(idx, V, rounding_mode="trunc")
                 cand_indices = idx.fmod(V)
-            cand_bbsz_idx = cand_beams.add(bbsz_offsets)
-            eos_mask = cand_indices.eq(eos) & cand_scores.ne(-math.inf)
-            eos_mask[:, :beam][cands_to_ignore] = False
-            eos_bbsz_idx = torch.masked_select(cand_bbsz_idx[:, :beam], mask=eos_mask[:, :beam])
+            # the bookkeeping: two HIP launches when the decoder has them (one candidate per lane:
+            # beam <= k <= 32), else the same steps in torch
+            bk = hip_bk if hip_bk is not None and beam <= k <= 32 else torch_bk
+            eos_mask, n_eos = bk.beam_eos_scan(cand_scores, cand_indices, cands_to_ignore, eos)
             finalized_sents = []
-            if eos_bbsz_idx.numel() > 0:
+            if int(n_eos) > 0:                    # the step's one host sync
+                cand_bbsz_idx = cand_beams.add(bbsz_offsets)
+                eos_bbsz_idx = torch.masked_select(cand_bbsz_idx[:, :beam], mask=eos_mask[:, :beam])
                 eos_scores = torch.masked_select(cand_scores[:, :beam], mask=eos_mask[:, :beam])
                 finalized_sents = self._finalize(step, eos_bbsz_idx, eos_scores, tokens, scores, finalized,
                                                  finished, max_len)
@@ -255,7 +320,6 @@ class SequenceGenerator:
                 eos_mask = eos_mask[batch_idxs]
                 cand_beams = cand_beams[batch_idxs]
                 bbsz_offsets = bbsz_offsets[:new_bsz]
-                cand_bbsz_idx = cand_beams.add(bbsz_offsets)
                 cand_scores = cand_scores[batch_idxs]
                 cand_indices = cand_indices[batch_idxs]
                 cands_to_ignore = cands_to_ignore[batch_idxs]
@@ -264,17 +328,13 @@ class SequenceGenerator:
                 bsz = new_bsz
             else:
                 batch_idxs = None
-            eos_mask[:, :beam] = ~((~cands_to_ignore) & (~eos_mask[:, :beam]))
-            active_mask = torch.add(eos_mask.type_as(cand_offsets) * cand_size, cand_offsets[: eos_mask.size(1)])
-            new_ignore, active_hypos = torch.topk(active_mask, k=beam, dim=1, largest=False)
-            cands_to_ignore = new_ignore.ge(cand_size)[:, :beam]
-            active_bbsz_idx = torch.gather(cand_bbsz_idx, 1, active_hypos).view(-1)
-            active_scores = torch.gather(cand_scores, 1, active_hypos)
-            tokens[:, : step + 1] = torch.index_select(tokens[:, : step + 1], 0, active_bbsz_idx)
-            tokens.view(bsz, beam, -1)[:, :, step + 1] = torch.gather(cand_indices, 1, active_hypos)
-            if step > 0:
-                scores[:, :step] = torch.index_select(scores[:, :step], 0, active_bbsz_idx)
-            scores.view(bsz, beam, -1)[:, :, step] = active_scores
+            if bk is hip_bk and (spare is None or spare[0].shape != tokens.shape):
+                spare = (torch.empty_like(tokens), torch.empty_like(scores))
+            prev = (tokens, scores)
+            cands_to_ignore, active_bbsz_idx, tokens, scores = bk.beam_advance(
+                eos_mask, cands_to_ignore, cand_scores, cand_indices, cand_beams, tokens, scores, step, spare)
+            if tokens is not prev[0]:             # written out of place: the old histories are the next spare
+                spare = prev
             reorder_state = active_bbsz_idx
         for s in range(len(finalized)):
             sc = torch.tensor([float(e["score"]) for e in finalized[s]])

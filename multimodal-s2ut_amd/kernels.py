@@ -1410,6 +1410,52 @@ def beam_topk(lprobs, prev_col, bsz, beam, V, k, first_step):
     return sc, tok, bm
 
 
+def _beam_check(name, dev, *specs):
+    for t, dtype, shape in specs:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name}: expected contiguous {dtype} {shape} on {dev}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+
+
+def beam_eos_scan(cand_scores, cand_indices, cands_to_ignore, eos):
+    """(eos_mask [bsz,k] bool, count int32 [1] on the device): the candidates that are </s> with a
+    finite score, cleared in the first `beam` columns where cands_to_ignore [bsz,beam] is set, and
+    the number of true entries in those columns."""
+    bsz, k = cand_scores.shape
+    beam = cands_to_ignore.shape[1]
+    dev = cand_scores.device
+    _beam_check("beam_eos_scan", dev, (cand_scores, torch.float32, (bsz, k)), (cand_indices, torch.int64, (bsz, k)),
+                (cands_to_ignore, torch.bool, (bsz, beam)))
+    mask = torch.empty(bsz, k, dtype=torch.bool, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    call("mms2ut_beam_eos_scan", cand_scores.data_ptr(), cand_indices.data_ptr(), cands_to_ignore.data_ptr(), bsz,
+         beam, k, int(eos), mask.data_ptr(), count.data_ptr(), _s())
+    return mask, count
+
+
+def beam_advance(eos_mask, cands_to_ignore, cand_scores, cand_indices, cand_beams, tokens, scores, step,
+                 tokens_out, scores_out):
+    """One search step's hypothesis update (mms2ut_beam_advance) -> (new cands_to_ignore [bsz,beam]
+    bool, active_bbsz_idx [bsz*beam] int64); tokens_out / scores_out receive the gathered histories
+    (columns [0, step+1] / [0, step]) and must not alias tokens / scores."""
+    bsz, k = cand_scores.shape
+    beam = cands_to_ignore.shape[1]
+    dev = cand_scores.device
+    N = bsz * beam
+    _beam_check("beam_advance", dev, (eos_mask, torch.bool, (bsz, k)), (cands_to_ignore, torch.bool, (bsz, beam)),
+                (cand_scores, torch.float32, (bsz, k)), (cand_indices, torch.int64, (bsz, k)),
+                (cand_beams, torch.int64, (bsz, k)), (tokens, torch.int64, (N, tokens.shape[1])),
+                (tokens_out, torch.int64, tuple(tokens.shape)), (scores, torch.float32, (N, scores.shape[1])),
+                (scores_out, torch.float32, tuple(scores.shape)))
+    new_ignore = torch.empty(bsz, beam, dtype=torch.bool, device=dev)
+    active = torch.empty(N, dtype=torch.int64, device=dev)
+    call("mms2ut_beam_advance", eos_mask.data_ptr(), cands_to_ignore.data_ptr(), cand_scores.data_ptr(),
+         cand_indices.data_ptr(), cand_beams.data_ptr(), bsz, beam, k, int(step), tokens.data_ptr(),
+         tokens_out.data_ptr(), tokens.shape[1], scores.data_ptr(), scores_out.data_ptr(), scores.shape[1],
+         new_ignore.data_ptr(), active.data_ptr(), _s())
+    return new_ignore, active
+
+
 def round_up(x, m):
     return (x + m - 1) // m * m
 

@@ -653,3 +653,70 @@ def build_parser():
     p.add_argument("--lenpen", type=float, default=1.0)
     p.add_argument("--min-len", type=int, default=1)
     return p
+
+
+# fairseq-generate's own defaults for the flags that belong to the run, not to the trained model:
+# they never come from the checkpoint's saved args
+GENERATE_DEFAULTS = {"beam": 5, "max_len_a": 0.0, "max_len_b": 200, "lenpen": 1.0, "min_len": 1, "nbest": 1,
+                     "gen_subset": "test", "max_tokens": None, "results_path": None, "path": None,
+                     "required_batch_size_multiple": 1, "skip_invalid_size_inputs_valid_test": False,
+                     "noise_config_yaml": None, "user_dir": None, "vocoder": None, "fp16": False,
+                     "multitask_config_yaml": None, "data": None}
+
+
+def build_generate_parser():
+    """The flags of the reference's fairseq-generate call (scripts/textless/2_inference.sh:34-44,
+    2_inference_all.sh:66-75).  Every default is SUPPRESS: the namespace holds only what the
+    command line gave, and ``merge_generate_args`` fills the rest from the checkpoint's saved
+    args (task and data flags) or from fairseq's defaults (``GENERATE_DEFAULTS``)."""
+    S = argparse.SUPPRESS
+    p = argparse.ArgumentParser("mms2ut-generate", argument_default=S)
+    p.add_argument("data", help="manifest directory ({gen-subset}.tsv, config.yaml, WAVs)")
+    p.add_argument("--path", required=True, help="checkpoint written by mms2ut-train (checkpoint_last.pt)")
+    p.add_argument("--task")
+    p.add_argument("--config-yaml")
+    p.add_argument("--multitask-config-yaml")
+    p.add_argument("--multimodal-translation-config-yaml")
+    p.add_argument("--noise-config-yaml")
+    p.add_argument("--target-is-code", action="store_true")
+    p.add_argument("--target-code-size", type=int)
+    p.add_argument("--max-source-positions", type=int)
+    p.add_argument("--max-target-positions", type=int)
+    p.add_argument("--gen-subset")
+    p.add_argument("--max-tokens", type=int)
+    p.add_argument("--skip-invalid-size-inputs-valid-test", action="store_true")
+    p.add_argument("--required-batch-size-multiple", type=int)
+    p.add_argument("--beam", type=int)
+    p.add_argument("--max-len-a", type=float)
+    p.add_argument("--max-len-b", type=int)
+    p.add_argument("--lenpen", type=float)
+    p.add_argument("--min-len", type=int)
+    p.add_argument("--nbest", type=int)
+    p.add_argument("--results-path")
+    p.add_argument("--seed", type=int)
+    # accepted for command-line compatibility, no effect
+    p.add_argument("--user-dir")
+    p.add_argument("--vocoder")
+    p.add_argument("--fp16", action="store_true")
+    return p
+
+
+def parse_generate_args(argv=None):
+    """-> Namespace of the flags given on the command line (nothing else)."""
+    p = build_generate_parser()
+    given = p.parse_args(argv)
+    if getattr(given, "required_batch_size_multiple", 1) != 1:
+        p.error("--required-batch-size-multiple must be 1 (batches are not rounded to a multiple)")
+    return given
+
+
+def merge_generate_args(given, saved):
+    """The run's args: the checkpoint's saved ``args`` (architecture, task and data flags), then
+    fairseq-generate's defaults for the run flags, then whatever the command line gave."""
+    out = dict(vars(saved)) if saved is not None else {}
+    out.update(GENERATE_DEFAULTS)
+    out.update(vars(given))
+    args = argparse.Namespace(**out)
+    if args.nbest < 1 or args.nbest > args.beam:
+        raise SystemExit(f"mms2ut-generate: --nbest {args.nbest} must be in [1, --beam {args.beam}]")
+    return args
