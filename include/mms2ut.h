@@ -417,6 +417,14 @@ int mms2ut_ls_xent_fwd(const mms2ut_half* logits, int64_t ld, const int64_t* tar
 int mms2ut_ls_xent_fwd_log(const mms2ut_half* logits, int64_t ld, const int64_t* target, int64_t rows,
                            int V, float eps, int pad_idx, float* lse, float* part, float* acc, float* call_out,
                            hipStream_t stream);
+/* validation scoring, forward only (no lse, no gradient): for every row whose target is not
+ * pad_idx, mms2ut_ls_xent_fwd's fp32 loss / nll and the argmax over columns [0, V) (ties to the
+ * lowest column).  stats[4] (fp64, device) += {loss, nll, ntokens, n_correct}: it accumulates
+ * over calls, the caller zeroes it once per split.  Sums are formed in fp64 from the per-row fp32
+ * values, counts are exact integers; block partials in part[4 * MMS_LS_XENT_PARTS] (fp64) are
+ * summed in a fixed order (bit-reproducible).  logits 8-byte aligned, ld % 4 == 0, ld >= V.      */
+int mms2ut_ls_xent_eval(const mms2ut_half* logits, int64_t ld, const int64_t* target, int64_t rows,
+                        int V, float eps, int pad_idx, double* part, double* stats, hipStream_t stream);
 /* dlogits = grad * ((1-eps-eps_i)(p - onehot) + eps_i(V p - 1)), 0 on pad rows; in place OK */
 int mms2ut_ls_xent_bwd(const mms2ut_half* logits, int64_t ld, const int64_t* target, int64_t rows,
                        int V, float eps, int pad_idx, const float* lse, const float* grad,

@@ -76,6 +76,87 @@ __global__ void __launch_bounds__(64) ls_xent_sum_kernel(const float* __restrict
   }
 }
 
+// Validation scoring: ls_xent_fwd_kernel's per-row arithmetic (same loads, same fp32 lse / nll /
+// smoothed loss) plus the row's argmax over [0, V), forward only: no lse, no gradient.  Each block
+// leaves {loss, nll, ntokens, n_correct} in fp64 (the fp32 row values are summed in fp64, the
+// counts are integers), part[k * gridDim.x + block]; ls_xent_eval_sum_kernel adds them in block
+// order, so a split's totals are bit-reproducible.
+template <int CPL>
+__global__ void __launch_bounds__(256) ls_xent_eval_kernel(const h16* __restrict__ z, long ld,
+                                                           const int64_t* __restrict__ target, long rows,
+                                                           int V, float eps, int pad, double* __restrict__ part) {
+  __shared__ double red[4][4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double loss = 0.0, nll = 0.0;
+  int ntok = 0, ncorrect = 0;
+  for (long row = (long)blockIdx.x * 4 + w; row < rows; row += (long)gridDim.x * 4) {
+    const int64_t t = target[row];   // wave-uniform: a pad row costs no logits traffic
+    if (t == pad) continue;
+    const h16* zr = z + row * ld;
+    float v[CPL][4];
+    float mx = -INFINITY, sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int j0 = (lane + c * 64) * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[c][e] = -INFINITY;
+      if (j0 < V) {
+        h16x4 q = *reinterpret_cast<const h16x4*>(zr + j0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (j0 + e < V) { v[c][e] = (float)q[e]; mx = fmaxf(mx, v[c][e]); sum += v[c][e]; }
+      }
+    }
+    mx = wave_max(mx);
+    sum = wave_sum(sum);
+    // argmax, ties to the lowest column: the lane's first column holding the wave maximum (its
+    // columns ascend with c, then e), then the wave minimum of those.  Column indices (< 2^14) are
+    // exact in fp32, so the minimum rides the wave_max network as a negated float.
+    float first = -(float)(1 << 24);   // no column equals the maximum (a row of NaNs): never correct
+#pragma unroll
+    for (int c = CPL - 1; c >= 0; --c)
+#pragma unroll
+      for (int e = 3; e >= 0; --e) {
+        const int j = (lane + c * 64) * 4 + e;
+        if (j < V && v[c][e] == mx) first = -(float)j;
+      }
+    const int amax = (int)-wave_max(first);
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) se += (v[c][e] == -INFINITY) ? 0.f : __expf(v[c][e] - mx);
+    se = wave_sum(se);
+    const float lse = mx + __logf(se);
+    // a target outside [0, V) poisons the sums instead of reading past the row
+    const float zt = (t >= 0 && t < V) ? (float)zr[t] : NAN;
+    const float eps_i = eps / (V - 1);
+    const float nl = lse - zt;
+    const float smooth = V * lse - sum;
+    nll += (double)nl;
+    loss += (double)((1.f - eps - eps_i) * nl + eps_i * smooth);
+    ntok += 1;
+    ncorrect += (amax == (int)t) ? 1 : 0;
+  }
+  if (lane == 0) { red[0][w] = loss; red[1][w] = nll; red[2][w] = (double)ntok; red[3][w] = (double)ncorrect; }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    part[(long)k * gridDim.x + blockIdx.x] = red[k][0] + red[k][1] + red[k][2] + red[k][3];
+  }
+}
+
+// stats[k] += the nb block partials of slot k, summed in a fixed order (lane-strided, then the
+// xor butterfly); one wave per slot
+__global__ void __launch_bounds__(256) ls_xent_eval_sum_kernel(const double* __restrict__ part, int nb,
+                                                               double* __restrict__ stats) {
+  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+  double s = 0.0;
+  for (int i = lane; i < nb; i += 64) s += part[(long)k * nb + i];
+  s = wave_sum_d(s);
+  if (lane == 0) stats[k] += s;
+}
+
 template <int CPL>
 __global__ void __launch_bounds__(256) ls_xent_bwd_kernel(const h16* __restrict__ z, long ld,
                                                           const int64_t* __restrict__ target, long rows,
@@ -352,6 +433,24 @@ extern "C" int mms2ut_ls_xent_fwd(const h16* logits, int64_t ld, const int64_t* 
                                   hipStream_t s) {
   MMS_REQUIRE(loss_out, "ls_xent: null loss");
   return mms2ut_ls_xent_fwd_log(logits, ld, target, rows, V, eps, pad_idx, lse, part, loss_out, nullptr, s);
+}
+
+extern "C" int mms2ut_ls_xent_eval(const h16* logits, int64_t ld, const int64_t* target, int64_t rows, int V,
+                                   float eps, int pad_idx, double* part, double* stats, hipStream_t s) {
+  MMS_REQUIRE(ld % 4 == 0 && ld >= V, "ls_xent_eval: ld must be a multiple of 4 and >= V");
+  MMS_REQUIRE(((uintptr_t)logits & 7) == 0, "ls_xent_eval: logits must be 8-byte aligned");
+  MMS_REQUIRE(V >= 2 && V <= 64 * 4 * 16, "ls_xent_eval: vocabulary size out of range (%d)", V);
+  MMS_REQUIRE(part && stats, "ls_xent_eval: null partials / stats");
+  if (rows == 0) return 0;
+  const int nb = (int)std::min<long>((rows + 3) / 4, MMS_LS_XENT_PARTS);
+  const int rc = pick_cpl_v(V, [&](auto C) {
+    hipLaunchKernelGGL((ls_xent_eval_kernel<decltype(C)::value>), dim3(nb), dim3(256), 0, s,
+                       logits, (long)ld, target, (long)rows, V, eps, pad_idx, part);
+    return mms::check_launch("ls_xent_eval");
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(ls_xent_eval_sum_kernel, dim3(1), dim3(256), 0, s, part, nb, stats);
+  return mms::check_launch("ls_xent_eval_sum");
 }
 
 extern "C" int mms2ut_ls_xent_bwd(const h16* logits, int64_t ld, const int64_t* target, int64_t rows, int V,

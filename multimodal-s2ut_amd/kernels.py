@@ -1179,6 +1179,23 @@ def ls_xent_fwd(logits, ld, target, rows, V, eps, pad, loss_out, call_out=None):
     return lse
 
 
+EVAL_LOSS, EVAL_NLL, EVAL_NTOKENS, EVAL_NCORRECT = range(4)
+
+
+def ls_xent_eval(logits, ld, target, rows, V, eps, pad, stats):
+    """Validation scoring, forward only: stats (fp64 device [4]) += {label-smoothed loss, nll,
+    non-pad targets, rows whose argmax over [0, V) is the target}.  Accumulates over calls (the
+    caller zeroes ``stats`` once per split); no host sync."""
+    assert stats.dtype == torch.float64 and stats.numel() == 4 and stats.is_contiguous()
+    _chk(logits)
+    _chk(target, torch.int64)
+    assert stats.is_cuda and target.numel() >= rows and logits.numel() >= rows * ld
+    part = _workspace("ls_xent_eval_part", 4 * LS_XENT_PARTS, logits.device, torch.float64)
+    call("mms2ut_ls_xent_eval", logits.data_ptr(), ld, target.data_ptr(), rows, V, float(eps), pad,
+         part.data_ptr(), stats.data_ptr(), _s())
+    return stats
+
+
 def set_f32(dst, vals):
     """dst[:len(vals)] = vals (fp32 device vector, <= 8 values) in one launch."""
     import ctypes

@@ -593,9 +593,19 @@ class SpeechToUnitCriterion:
         return True
 
 
+class _TrainParser(argparse.ArgumentParser):
+    """--max-tokens-valid defaults to the value of --max-tokens (fairseq DatasetConfig)."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, "max_tokens_valid", None) is None:
+            ns.max_tokens_valid = getattr(ns, "max_tokens", None)
+        return ns, rest
+
+
 def build_parser():
     """Flag subset of the canonical command (scripts/textless/1_train.sh:105-125)."""
-    p = argparse.ArgumentParser("mms2ut-train")
+    p = _TrainParser("mms2ut-train")
     MultiModalSpeechToSpeechTask.add_args(p)
     p.add_argument("--task", default="multimodal_speech_to_speech")
     p.add_argument("--arch", default="mm_s2ut_transformer")
@@ -634,6 +644,20 @@ def build_parser():
     p.add_argument("--restore-file", default="checkpoint_last.pt")
     p.add_argument("--save-interval-updates", type=int, default=0)
     p.add_argument("--log-interval", type=int, default=10)
+    # validation during training and checkpoint_best.pt (validation.ValidationPolicy; fairseq's
+    # dataset / checkpoint flag defaults)
+    p.add_argument("--max-tokens-valid", type=int, default=None, help="default: --max-tokens")
+    p.add_argument("--validate-interval", type=int, default=1)
+    p.add_argument("--validate-interval-updates", type=int, default=0)
+    p.add_argument("--validate-after-updates", type=int, default=0)
+    p.add_argument("--disable-validation", action="store_true")
+    p.add_argument("--skip-invalid-size-inputs-valid-test", action="store_true")
+    p.add_argument("--best-checkpoint-metric", default="loss", choices=("loss", "nll_loss", "ppl", "accuracy"))
+    p.add_argument("--maximize-best-checkpoint-metric", action="store_true")
+    p.add_argument("--patience", type=int, default=-1)
+    p.add_argument("--report-accuracy", action="store_true", help="teacher-forced unit accuracy in valid records")
+    p.add_argument("--no-epoch-checkpoints", action="store_true",
+                   help="accepted, no effect: only checkpoint_last.pt and checkpoint_best.pt are written")
     # accepted for command-line compatibility with 1_train.sh (no effect on the training step)
     p.add_argument("--distributed-world-size", type=int, default=None)
     p.add_argument("--tensorboard-logdir", default=None)

@@ -247,6 +247,14 @@ class _LSXentFn(torch.autograd.Function):
         return logits, None, None, None, None, None
 
 
+def label_smoothed_eval(logits, target, V, eps, pad, stats):
+    """Validation scoring of padded logits [rows, ld] (no autograd, no lse, no gradient): stats
+    (fp64 device [4]) += {label_smoothed_ce's loss, nll, non-pad targets, teacher-forced argmax
+    hits} — fairseq's valid logging sums with --report-accuracy, accumulated on the device."""
+    rows, ld = logits.shape
+    return K.ls_xent_eval(logits, ld, target.reshape(-1), rows, V, eps, pad, stats)
+
+
 def label_smoothed_ce(logits, target, V, eps, pad, acc=None):
     """fairseq label_smoothed_nll_loss(lprobs=log_softmax(logits.float()), reduce=sum).
     acc: an optional fp32 device [2] (e.g. a trainer's step log) that {loss, nll} are added to."""

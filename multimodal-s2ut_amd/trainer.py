@@ -27,6 +27,8 @@ Buffer access: the Adam update runs deferred on the side stream (optim.FP16Adam.
 ``opt.stats`` and the next forward wait by themselves.
 """
 
+import math
+
 import numpy as np
 import torch
 
@@ -54,6 +56,22 @@ class _ScriptedDraws:
         return self.vals.pop(0)
 
 
+def valid_stats(loss, nll, ntokens, n_correct, nsentences):
+    """fairseq's valid stats from a split's sums (natural-log loss / nll sums over target tokens):
+    loss and nll_loss per token in base 2, ppl = 2**nll_loss, accuracy in percent.  An empty split
+    gives NaN metrics (never "best")."""
+    ln2 = math.log(2.0)
+    per = (lambda x: x / ntokens / ln2) if ntokens > 0 else (lambda x: float("nan"))
+    nll2 = per(nll)
+    try:
+        ppl = 2.0 ** nll2
+    except OverflowError:
+        ppl = float("inf")
+    return {"loss": per(loss), "nll_loss": nll2, "ppl": ppl,
+            "accuracy": 100.0 * n_correct / ntokens if ntokens > 0 else float("nan"),
+            "ntokens": int(ntokens), "nsentences": int(nsentences)}
+
+
 class Trainer:
     def __init__(self, model, lr=5e-4, betas=(0.9, 0.98), clip_norm=10.0, warmup_updates=10000,
                  warmup_init_lr=1e-7, init_scale=128.0, bucket_mb=64.0, world_size=1, update_freq=1,
@@ -71,6 +89,7 @@ class Trainer:
         self.world = world_size
         self.acc = None   # fp32 gradient accumulator (update_freq > 1), allocated on first use
         self.log = torch.zeros(5, dtype=torch.float32, device=model.params.flat.device)
+        self.vstats = None     # fp64 validation sums (validate), allocated on first use
         self.grad_tap = None   # optional callable(flat fp16 grad) run right before the optimizer (tests)
         # The step's critical path (forward, dgrad chain, optimizer) runs on a high-priority stream
         # so the hardware dispatcher prefers its workgroups over the weight-gradient side stream's
@@ -253,6 +272,59 @@ class Trainer:
                                                   self.cfg["label_smoothing"], self.cfg["padding_idx"])
         m.train()
         return loss, nll
+
+    def validate(self, batches):
+        """One validation pass (fairseq validate(): the criterion's logging outputs summed over the
+        split).  batches: an iterable of this rank's runtime.DeviceBatch (ranks may hold unequal
+        counts, none included).  Each batch runs the eval-mode forward and the forward-only scoring
+        kernel (K.ls_xent_eval) on the trainer's stream, accumulating {loss, nll, ntokens,
+        n_correct} in one fp64 device vector: no host read per batch, one summed all-reduce and one
+        host read at the end.  Auxiliary multitask heads are not run.  Returns fairseq's valid
+        stats: loss / nll_loss per target token in base 2, ppl = 2**nll_loss, accuracy =
+        100 * n_correct / ntokens (--report-accuracy), ntokens, nsentences.
+
+        Draws nothing from numpy's stream, the dropout stream or the device step seed, and leaves
+        the optimizer, the gradient buffer and the captured graphs untouched."""
+        m, cfg = self.model, self.cfg
+        dev = m.params.flat.device
+        if self.vstats is None:
+            self.vstats = torch.zeros(5, dtype=torch.float64, device=dev)   # kernel's [4] + nsentences
+        st = self.vstats
+        cur = torch.cuda.current_stream() if self.stream is not None else None
+        run = torch.cuda.stream(self.stream) if self.stream is not None else K._NULLCTX
+        nsent = 0
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad():
+                if cur is not None:
+                    K.stream_wait(self.stream, cur)
+                with run:
+                    st.zero_()
+                for batch in batches:          # the loader uploads on the caller's stream
+                    if cur is not None:
+                        K.stream_wait(self.stream, cur)
+                    with run:
+                        mt, batch.mt = batch.mt, None      # no multitask heads in validation
+                        try:
+                            logits, _ = runtime.model_outputs(m, batch)
+                        finally:
+                            batch.mt = mt
+                        runtime.label_smoothed_eval(logits, batch.target, cfg["vocab_size"],
+                                                    cfg["label_smoothing"], cfg["padding_idx"], st[:4])
+                        del logits
+                    nsent += int(batch.nsentences)
+                    if cur is not None:
+                        cur.wait_stream(self.stream)    # hand-back, as train_step: the batch may be freed
+                with run:
+                    st[4:].fill_(float(nsent))
+                    all_reduce_scalars(st)
+                if cur is not None:
+                    cur.wait_stream(self.stream)
+                loss, nll, ntok, ncorrect, nsent = st.tolist()   # the pass's one host read
+        finally:
+            m.train(was_training)
+        return valid_stats(loss, nll, ntok, ncorrect, nsent)
 
     # ------------------------------------------------------------------ checkpoints
     def completed_updates(self):
