@@ -1026,6 +1026,38 @@ int mms2ut_gated_fusion_bwd(const mms2ut_gated_fusion* f, const mms2ut_half* dre
 enum { MMS_OP_LAYER = 0, MMS_OP_CONV1D_GLU = 1, MMS_OP_GATED_FUSION = 2 };
 int mms2ut_workspace_size(int op, const void* desc, int64_t* sizes);
 
+/* ---------------------------------------------------------------- ViT attention rollout
+ * What the reference's scripts/extract_feature/vit_rollout.py computes from a hook on timm's
+ * attn_drop, without the [H][T][T] probabilities (csrc/rollout.hip).  Everything is fp32 and every
+ * run gives the same bits.
+ *
+ * rollout_probs_f16: out[b][i][j] (row stride T, batch stride out_batch floats) = the mean, max or
+ * min over heads h of softmax_j(scale * q[b T + i][h hd ..] . k[b T + j][h hd ..]) -- the packed q|k|v
+ * rows mha_varlen_fwd reads (row strides ldq, ldk in elements, multiples of 8), all T keys, no
+ * padding.  The mean adds heads 0 .. H - 1 in order and multiplies by 1 / H.  hd: 64, 96 or 128;
+ * T <= MMS_ROLLOUT_MAX_T.
+ *
+ * rollout_discard_f32: in each of nmat contiguous matrices of n non-negative floats, the k smallest
+ * become 0, except flat index 0, which is counted among the k but kept.  Among entries equal to the
+ * k-th smallest, lower flat indices go first (the order of a stable sort).  Membership is decided on
+ * the bit patterns alone.  n <= MMS_ROLLOUT_MAX_T^2, 0 <= k <= n.
+ *
+ * rollout_chain_f32: a [B][L][T][T], the processed matrices of layers 1 .. L.  Per image: a_l =
+ * (F_l + I) / 2, s_i = sum_j a_l[i][j], a_l[i][j] /= s_j (MMS_ROLLOUT_NORM_REFERENCE: the reference's
+ * a / a.sum(-1)) or /= s_i (MMS_ROLLOUT_NORM_ROW); R = a_L ... a_1; mask[b][j] = R[0][1 + j] /
+ * max_j R[0][1 + j], [B][T - 1]; the sums between the fp32 input and the fp32 mask are carried in
+ * double (sums: a workspace of B L T doubles, the s_i of every matrix).  bad[b] = 1 and a zero mask
+ * where the maximum is not positive or an entry is not finite.                                  */
+#define MMS_ROLLOUT_MAX_T 640
+enum { MMS_ROLLOUT_MEAN = 0, MMS_ROLLOUT_MAX = 1, MMS_ROLLOUT_MIN = 2 };
+enum { MMS_ROLLOUT_NORM_REFERENCE = 0, MMS_ROLLOUT_NORM_ROW = 1 };
+int mms2ut_rollout_probs_f16(const mms2ut_half* q, const mms2ut_half* k, int64_t ldq, int64_t ldk, int B, int H,
+                             int T, int hd, float scale, int fusion, float* out, int64_t out_batch,
+                             hipStream_t stream);
+int mms2ut_rollout_discard_f32(float* x, int nmat, int64_t n, int64_t k, hipStream_t stream);
+int mms2ut_rollout_chain_f32(const float* a, int B, int L, int T, int normalization, double* sums, float* mask,
+                             int32_t* bad, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,7 @@ ASR_CONV_ARGS = _packer(AsrConvArgs)
 HUBERT_GN_PARTS, KMEANS_LO_SCALE = 256, 2048              # include/mms2ut.h MMS_HUBERT_GN_PARTS, MMS_KMEANS_LO_SCALE
 
 VISION_TILE_BYTES, VISION_MAX_SIDE = 49152, 65535         # include/mms2ut.h MMS_VISION_*
+ROLLOUT_MAX_T = 640                                       # include/mms2ut.h MMS_ROLLOUT_MAX_T
 
 
 class ImageDesc(C.Structure):
@@ -309,6 +310,9 @@ SIGNATURES = {
     "mms2ut_kmeans_fold": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mms2ut_vision_patches": (i32, [vp, i64, vp, i32, vp, i64, vp, vp, i32, i32, i32, vp]),
     "mms2ut_nonfinite_rows_f16": (i32, [vp, i64, i32, i64, vp, vp]),
+    "mms2ut_rollout_probs_f16": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, f32, i32, vp, i64, vp]),
+    "mms2ut_rollout_discard_f32": (i32, [vp, i32, i64, i64, vp]),
+    "mms2ut_rollout_chain_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "mms2ut_layer_arena": (i32, [vp, vp, vp]),
     "mms2ut_layer_scratch": (i32, [vp, f32, vp, vp]),
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),

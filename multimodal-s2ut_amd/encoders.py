@@ -154,16 +154,19 @@ def layer_dict(w, p, d, Fd, names):
             "w1": t(fc1, "weight", Fd, d), "b1": t(fc1, "bias", Fd), "w2": t(fc2, "weight", d, Fd), "b2": t(fc2, "bias", d)}
 
 
-def transformer_layers(Hb, layers, H, eps, lens32=None, *, post_ln=False):
+def transformer_layers(Hb, layers, H, eps, lens32=None, *, post_ln=False, on_qkv=None):
     """Transformer layers (packed q|k|v with bias, erf-GELU MLP, both residuals in the GEMM epilogue) over
     fp16 [B, Tmax, d] -> fp16 [B * Tmax, d]; layers: layer_dict()s.  Pre-LN (wav2vec2 with stable layer
-    norm, ViT): each LayerNorm feeds its sublayer.  post_ln (HuBERT-base): it follows the residual sum."""
+    norm, ViT): each LayerNorm feeds its sublayer.  post_ln (HuBERT-base): it follows the residual sum.
+    on_qkv(layer index, qkv fp16 [B * Tmax, 3 d]) is called right after a layer's qkv GEMM, on the same stream."""
     B, Tm, d = Hb.shape
     R, hd = B * Tm, d // H
     X = Hb.reshape(R, d)
-    for L in layers:
+    for l, L in enumerate(layers):
         y = X if post_ln else K.layernorm(X, L["ln1_g"], L["ln1_b"], eps)[0]
         qkv = K.linear(y, L["wqkv"], L["bqkv"])
+        if on_qkv is not None:
+            on_qkv(l, qkv)
         o = torch.empty(R, d, dtype=K.F16, device=X.device)
         K.mha_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], o, 3 * d, 3 * d, 3 * d, d, B, H, Tm, Tm, hd, hd ** -0.5,
                   key_len=lens32)

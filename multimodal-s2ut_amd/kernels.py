@@ -1898,4 +1898,82 @@ def nonfinite_rows(x):
     return bad
 
 
+# ============================================================================ ViT attention rollout
+
+ROLLOUT_MAX_T = _lib.ROLLOUT_MAX_T
+ROLLOUT_FUSIONS = {"mean": 0, "max": 1, "min": 2}                   # include/mms2ut.h MMS_ROLLOUT_*
+ROLLOUT_NORMALIZATIONS = {"reference": 0, "row": 1}
+
+
+def rollout_discard_count(T, discard_ratio):
+    """How many entries of a [T, T] matrix the discard step takes: the reference's int(T * T * ratio)."""
+    if not 0.0 <= discard_ratio <= 1.0:
+        raise ValueError(f"discard_ratio must be in [0, 1], got {discard_ratio}")
+    return int(T * T * discard_ratio)
+
+
+def rollout_probs(qkv, B, H, T, head_fusion="mean", out=None):
+    """Head-fused attention probabilities of one layer from its packed fp16 qkv [B * T, 3 d] (the buffer
+    mha_fwd reads: q | k | v column blocks, heads of hd = d / H columns, scale hd^-0.5) -> fp32 [B, T, T], the
+    mean / max / min over heads of softmax(q k^T scale); out: a [B, T, T] view with contiguous matrices."""
+    _chk(qkv)
+    if head_fusion not in ROLLOUT_FUSIONS:
+        raise ValueError(f"head_fusion '{head_fusion}' (one of {', '.join(ROLLOUT_FUSIONS)})")
+    if T > ROLLOUT_MAX_T:
+        raise NotImplementedError(f"rollout_probs: {T} tokens exceed the kernel's limit of {ROLLOUT_MAX_T}")
+    if qkv.dim() != 2 or qkv.shape[0] != B * T or qkv.shape[1] % (3 * H) or qkv.stride(1) != 1 or T < 1:
+        raise ValueError(f"rollout_probs: qkv [B * T, 3 d] with d a multiple of H expected, got {tuple(qkv.shape)}")
+    d = qkv.shape[1] // 3
+    hd = d // H
+    if hd not in FLASH_HD:
+        raise NotImplementedError(f"rollout_probs: head dim {hd} is not supported ({FLASH_HD})")
+    if out is None:
+        out = torch.empty(B, T, T, dtype=torch.float32, device=qkv.device)
+    _chk(out, torch.float32)
+    if tuple(out.shape) != (B, T, T) or (T > 1 and out.stride()[1:] != (T, 1)) or (B > 1 and out.stride(0) < T * T):
+        raise ValueError(f"rollout_probs: out must be [B, T, T] = {(B, T, T)} with contiguous matrices")
+    k = qkv[:, d:]
+    call("mms2ut_rollout_probs_f16", qkv.data_ptr(), k.data_ptr(), qkv.stride(0), qkv.stride(0), B, H, T, hd,
+         hd ** -0.5, ROLLOUT_FUSIONS[head_fusion], out.data_ptr(), out.stride(0) if B > 1 else T * T, _s())
+    return out
+
+
+def rollout_discard(x, k):
+    """In place on contiguous fp32 [..., T, T] of non-negative values: per matrix the k smallest entries
+    become 0 (ties at the k-th value: lower flat index first), flat index 0 is counted but kept."""
+    _chk(x, torch.float32)
+    if x.dim() < 2 or x.shape[-1] != x.shape[-2] or not x.is_contiguous():
+        raise ValueError(f"rollout_discard: contiguous [..., T, T] expected, got {tuple(x.shape)}")
+    T = x.shape[-1]
+    if T > ROLLOUT_MAX_T:
+        raise NotImplementedError(f"rollout_discard: {T} tokens exceed the kernel's limit of {ROLLOUT_MAX_T}")
+    n = T * T
+    if not 0 <= k <= n:
+        raise ValueError(f"rollout_discard: k must be in [0, {n}], got {k}")
+    if x.numel() and k:
+        call("mms2ut_rollout_discard_f32", x.data_ptr(), x.numel() // n, n, int(k), _s())
+    return x
+
+
+def rollout_chain(a, normalization="reference"):
+    """Processed matrices fp32 [B, L, T, T] (layers 1 .. L) -> (mask fp32 [B, T - 1], bad int32 [B]): the
+    normalisation of each layer and row 0 of a_L ... a_1 over its maximum; bad[b] = 1 (and a zero mask) where
+    that maximum is not positive or an entry is not finite."""
+    _chk(a, torch.float32)
+    if normalization not in ROLLOUT_NORMALIZATIONS:
+        raise ValueError(f"normalization '{normalization}' (one of {', '.join(ROLLOUT_NORMALIZATIONS)})")
+    if a.dim() != 4 or a.shape[2] != a.shape[3] or a.shape[1] < 1 or a.shape[2] < 2 or not a.is_contiguous():
+        raise ValueError(f"rollout_chain: contiguous [B, L, T, T] with L >= 1, T >= 2 expected, got {tuple(a.shape)}")
+    B, L, T, _ = a.shape
+    if T > ROLLOUT_MAX_T:
+        raise NotImplementedError(f"rollout_chain: {T} tokens exceed the kernel's limit of {ROLLOUT_MAX_T}")
+    mask = torch.empty(B, T - 1, dtype=torch.float32, device=a.device)
+    bad = torch.zeros(B, dtype=torch.int32, device=a.device)
+    if B:
+        sums = torch.empty(B, L, T, dtype=torch.float64, device=a.device)       # every matrix' row sums
+        call("mms2ut_rollout_chain_f32", a.data_ptr(), B, L, T, ROLLOUT_NORMALIZATIONS[normalization], sums.data_ptr(),
+             mask.data_ptr(), bad.data_ptr(), _s())
+    return mask, bad
+
+
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]

@@ -35,16 +35,34 @@ DATASETS = {"train": ("flickr30k", "train.txt", "train"), "val": ("flickr30k", "
             "test2017": ("test2017", "test_2017_flickr.txt", "test1"),
             "testcoco": ("testcoco", "test_2017_mscoco.txt", "test2")}
 TABLE_CACHE_INTS = 16 << 20     # the device coefficient tables are dropped and rebuilt past 64 MiB
+# timm's CLIP-style ViTs (vision_transformer.py, pre_norm=True, no patch bias): norm_pre after the position
+# embeddings; their pretrained cfgs carry the OpenAI-CLIP mean and std.  name -> (width, heads, depth)
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+PRE_NORM_MODELS = {"vit_base_patch16_clip_384": (768, 12, 12),
+                   "vit_base_patch16_clip_384.laion2b_ft_in12k_in1k": (768, 12, 12)}
+# the rollout's per-layer matrices [chunk, layers, T, T] fp32 never exceed this; a batch is cut into chunks
+ROLLOUT_WS_BYTES = 256 << 20
 
 
 class NonFiniteFeatures(RuntimeError):
     """An image's features hold inf or NaN (fp16 activations overflowed): nothing is written."""
 
 
+class EmptyRollout(RuntimeError):
+    """An image's rollout reaches no patch (its maximum is 0) or holds inf or NaN: nothing is written."""
+
+
 def model_config(name):
-    """{d, heads, layers, mlp, image_size, patch} of a timm model name."""
+    """{d, heads, layers, mlp, image_size, patch} of a timm model name; the CLIP-style models add pre_norm,
+    mean and std."""
+    if name in PRE_NORM_MODELS:
+        d, H, L = PRE_NORM_MODELS[name]
+        return {"d": d, "heads": H, "layers": L, "mlp": 4 * d, "image_size": 384, "patch": 16, "pre_norm": True,
+                "mean": CLIP_MEAN, "std": CLIP_STD}
+    if "clip" in name and (name.endswith(".openai") or "quickgelu" in name):
+        raise NotImplementedError(f"model '{name}' uses QuickGELU, which is not supported (only erf-GELU)")
     if name not in MODELS:
-        raise ValueError(f"model '{name}' is not supported (one of {', '.join(sorted(MODELS))})")
+        raise ValueError(f"model '{name}' is not supported (one of {', '.join(sorted({**MODELS, **PRE_NORM_MODELS}))})")
     d, H, L = MODELS[name]
     return {"d": d, "heads": H, "layers": L, "mlp": 4 * d, "image_size": 384, "patch": 16}
 
@@ -128,11 +146,14 @@ class ViTFeatures:
     """timm VisionTransformer.forward_features (num_classes=0: every token after the final norm) on raw
     RGB images, with timm's eval transform in front."""
 
-    def __init__(self, state_dict, config, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), interpolation="bicubic",
-                 device="cuda"):
+    def __init__(self, state_dict, config, mean=None, std=None, interpolation="bicubic", device="cuda"):
         if interpolation != "bicubic":
             raise NotImplementedError(f"interpolation '{interpolation}' is not supported (only \"bicubic\")")
         c = self.cfg = dict(config)
+        # the transform's mean and std: the arguments, else the config's (pre-norm models), else timm's 0.5
+        mean = c.get("mean", (0.5, 0.5, 0.5)) if mean is None else mean
+        std = c.get("std", (0.5, 0.5, 0.5)) if std is None else std
+        self.pre_norm = bool(c.get("pre_norm", False))
         self.device = dev = torch.device(device)
         d, H, Fd, S, P = c["d"], c["heads"], c["mlp"], c["image_size"], c["patch"]
         if d % H or d // H not in K.FLASH_HD:
@@ -146,7 +167,12 @@ class ViTFeatures:
                     hints={"pos_embed": " (position embeddings are not interpolated to other image sizes)"})
         get, f16 = w.get, w.f16
         self.patch_w = f16(get("patch_embed.proj.weight", (d, 3, P, P)).reshape(d, 3 * P * P))
-        self.patch_b = f16(get("patch_embed.proj.bias", (d,)))
+        if self.pre_norm and "patch_embed.proj.bias" not in state_dict:      # timm: bias = not pre_norm
+            self.patch_b = torch.zeros(d, dtype=K.F16, device=dev)
+        else:
+            self.patch_b = f16(get("patch_embed.proj.bias", (d,)))
+        if self.pre_norm:
+            self.pre_g, self.pre_b = f16(get("norm_pre.weight", (d,))), f16(get("norm_pre.bias", (d,)))
         pos, cls = get("pos_embed", (1, T, d))[0], get("cls_token", (1, 1, d))[0, 0]
         self.row0 = f16((cls + pos[0]).reshape(1, d))            # the class token's row, rounded once
         self.pos = f16(pos[1:])
@@ -226,16 +252,66 @@ class ViTFeatures:
         K.gemm(patches, self.patch_w, X[:, 1:], N, d, Kd, lda=Kd, ldb=Kd, ldc=d, batch=B, sA=(N * Kd, 0), sC=(T * d, 0),
                epi=K.EPI_DROP_RESID, bias=self.patch_b, aux=self.pos, ldaux=d)
         K.copy2d(self.row0.expand(B, d), X[:, 0], B, d)
+        if self.pre_norm:
+            X = K.layernorm(X.view(B * T, d), self.pre_g, self.pre_b, LN_EPS)[0].view(B, T, d)
         return X
 
-    def tokens(self, X):
+    def tokens(self, X, on_qkv=None):
         """fp16 [B, T, d] -> fp16 [B, T, d]: the blocks and the final norm."""
         B, T, d = X.shape
-        Y = transformer_layers(X, self.layers, self.H, LN_EPS)
+        Y = transformer_layers(X, self.layers, self.H, LN_EPS, on_qkv=on_qkv)
         return K.layernorm(Y, self.norm_g, self.norm_b, LN_EPS)[0].view(B, T, d)
 
     def forward_device(self, images):
         return self.tokens(self.embed(self.patches(images)))
+
+    # ---------------------------------------------------------------------------------- rollout
+
+    def rollout_chunk(self):
+        """Images one rollout pass may hold: its [chunk, layers, T, T] fp32 workspace stays within
+        ROLLOUT_WS_BYTES (at least one image)."""
+        return max(1, ROLLOUT_WS_BYTES // (4 * max(len(self.layers), 1) * self.T * self.T))
+
+    def rollout_device(self, images, head_fusion="mean", discard_ratio=0.9, normalization="reference", keep_fused=False):
+        """One chunk (at most rollout_chunk() images) on the device -> (mask fp32 [B, T - 1], bad int32 [B],
+        features fp16 [B, T, d] of the same forward, the fused matrices before the discard fp32 [B, L, T, T] if
+        keep_fused else None).  Each layer's head-fused probabilities are formed from the qkv buffer the
+        attention kernel reads, straight into the workspace; then one discard and one chain launch."""
+        B, T, L = len(images), self.T, len(self.layers)
+        if head_fusion not in K.ROLLOUT_FUSIONS:
+            raise ValueError(f"head_fusion '{head_fusion}' (one of {', '.join(K.ROLLOUT_FUSIONS)})")
+        if normalization not in K.ROLLOUT_NORMALIZATIONS:
+            raise ValueError(f"normalization '{normalization}' (one of {', '.join(K.ROLLOUT_NORMALIZATIONS)})")
+        k = K.rollout_discard_count(T, discard_ratio)
+        if T > K.ROLLOUT_MAX_T:
+            raise NotImplementedError(f"rollout: {T} tokens exceed the kernels' limit of {K.ROLLOUT_MAX_T}")
+        if L < 1 or not 1 <= B <= self.rollout_chunk():
+            raise ValueError(f"rollout: 1 .. {self.rollout_chunk()} images per pass and at least one layer expected")
+        ws = torch.empty(B, L, T, T, dtype=torch.float32, device=self.device)
+        Y = self.tokens(self.embed(self.patches(images)),
+                        on_qkv=lambda l, qkv: K.rollout_probs(qkv, B, self.H, T, head_fusion, out=ws[:, l]))
+        fused = ws.clone() if keep_fused else None
+        K.rollout_discard(ws, k)
+        mask, bad = K.rollout_chain(ws, normalization)
+        return mask, bad, Y, fused
+
+    def rollout(self, images, head_fusion="mean", discard_ratio=0.9, normalization="reference"):
+        """Attention rollout of each image, as the reference's vit_rollout.py computes it for a batch of one
+        -> host fp32 [B, S/P, S/P], each map divided by its maximum.  normalization "reference" divides
+        column j by the sum of row j (the reference's a / a.sum(-1)); "row" divides each row by its own sum.
+        The batch is processed rollout_chunk() images at a time."""
+        images = list(images)
+        n = self.S // self.P
+        out = torch.empty(len(images), n, n, dtype=torch.float32)
+        step = self.rollout_chunk()
+        for i in range(0, len(images), step):
+            mask, bad, _, _ = self.rollout_device(images[i:i + step], head_fusion, discard_ratio, normalization)
+            mask, bad = mask.cpu(), bad.cpu()
+            for b, flag in enumerate(bad.tolist()):
+                if flag:
+                    raise EmptyRollout(f"image {i + b} of the batch: the rollout is empty or non-finite; nothing written")
+            out[i:i + mask.shape[0]] = mask.view(-1, n, n)
+        return out
 
     def features(self, images, out=None):
         """fp32 [B, T, d] on the host (into out, if given): fp16 over PCIe into a pinned buffer kept between
@@ -313,6 +389,48 @@ def extract_dataset(model, root, dataset, save_dir, batch_size=32, num_workers=8
     path = os.path.join(save_dir, name + ".pth")
     torch.save(feats, path)
     return path, tuple(feats.shape)
+
+
+def overlay(image, mask, alpha=0.6):
+    """Presentation only, on the host: uint8 [h, w, 3] image with the rollout mask [n, n] (values in [0, 1])
+    resized to it (PIL bilinear) and blended over it towards red, weight alpha * mask -> uint8 [h, w, 3]."""
+    from PIL import Image
+    image = np.asarray(image)
+    h, w, _ = image.shape
+    m8 = np.clip(np.rint(np.asarray(mask, dtype=np.float64) * 255.0), 0, 255).astype(np.uint8)
+    m = np.asarray(Image.fromarray(m8).resize((w, h), Image.BILINEAR), dtype=np.float64)[..., None] * (alpha / 255.0)
+    heat = np.array([255.0, 0.0, 0.0])
+    return np.clip(np.rint(image * (1.0 - m) + heat * m), 0, 255).astype(np.uint8)
+
+
+def rollout_files(model, paths, batch_size=8, num_workers=8, head_fusion="mean", discard_ratio=0.9,
+                  normalization="reference", overlay_dir=None, progress=None):
+    """fp32 [N, S/P, S/P] rollout masks of image files, in order, decoded on a thread pool as extract_files
+    does.  overlay_dir: also one PNG per image there, {file's base name}_rollout.png, the overlay()."""
+    if batch_size < 1 or num_workers < 1:
+        raise ValueError("batch_size and num_workers must be >= 1")
+    paths = list(paths)
+    n = model.S // model.P
+    out = torch.empty(len(paths), n, n, dtype=torch.float32)
+    batches = [paths[i:i + batch_size] for i in range(0, len(paths), batch_size)]
+    if overlay_dir:
+        from PIL import Image
+        os.makedirs(overlay_dir, exist_ok=True)
+    with cf.ThreadPoolExecutor(max_workers=num_workers) as pool:
+        pending = [pool.submit(decode_image, p) for p in batches[0]] if batches else []
+        done = 0
+        for i, batch in enumerate(batches):
+            images = [f.result() for f in pending]
+            pending = [pool.submit(decode_image, p) for p in batches[i + 1]] if i + 1 < len(batches) else []
+            out[done:done + len(images)] = model.rollout(images, head_fusion, discard_ratio, normalization)
+            if overlay_dir:
+                for j, (p, im) in enumerate(zip(batch, images)):
+                    name = os.path.splitext(os.path.basename(p))[0] + "_rollout.png"
+                    Image.fromarray(overlay(im, out[done + j].numpy())).save(os.path.join(overlay_dir, name))
+            done += len(images)
+            if progress:
+                progress(done, len(paths))
+    return out
 
 
 def print_progress(done, total):

@@ -23,7 +23,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dataset", required=True, choices=["train", "val", "test2016", "test2017", "testcoco"])
     ap.add_argument("--path", required=True, help="directory of the list files and the *-images directories")
-    ap.add_argument("--model", required=True, help="vit_{tiny,small,base,large}_patch16_384")
+    ap.add_argument("--model", required=True, help="vit_{tiny,small,base,large}_patch16_384, vit_base_patch16_clip_384[.laion2b_ft_in12k_in1k]")
     ap.add_argument("--checkpoint-path", required=True, help="timm-layout state dict (.pth / .bin / .safetensors)")
     ap.add_argument("--save-dir", required=True)
     ap.add_argument("--batch-size", type=int, default=32, help="images per device batch")
