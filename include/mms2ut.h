@@ -820,6 +820,75 @@ int mms2ut_kmeans_assign(const void* X, int64_t ldx, int R, int d, const void* c
 int mms2ut_kmeans_fold(const float* pscore, const int32_t* pidx, int nchunks, int B, int Tmax, const int32_t* lens,
                        int32_t* code, int32_t* merged, int32_t* count, int32_t* bad, hipStream_t stream);
 
+/* ---------------------------------------------------------------- unit codebook training (k-means)
+ * scikit-learn's MiniBatchKMeans.fit on fp16 rows X [N, d] (d a multiple of 8, 16-byte aligned rows) --
+ * csrc/kmeans.hip, kmeans.py.  The assignment is mms2ut_kmeans_assign.  No float atomics: every sum has a
+ * fixed order and every run gives the same bits.
+ *
+ * `state` (where an entry takes one; may be NULL outside a fit): MMS_KMEANS_STATE doubles, zeroed before a
+ * fit: [0] steps run, [1] the EWA inertia, [2] its minimum, [3] steps without improvement, [4] done.  Once
+ * done is set, every kernel that was given the state returns without writing.
+ *
+ * row_norms: norms[r] = |X_r|^2 (fp32 per lane, the lanes added in double).
+ * gather: out[r] = X[idx[r]] (fp16, or fp32 with wide != 0; contiguous rows of d), norms_out[r] =
+ *   norms[idx[r]] (both NULL: no norms).  Indices may repeat; one outside [0, N) is clamped.
+ * train_fold: code[r] / best[r] = the best (index, score) over the chunks in chunk order of
+ *   mms2ut_kmeans_assign's partials (the lowest index wins a tie); partials[b] = the sum over block b's 256
+ *   rows of max(xnorm[r] + best[r], 0) in double ((R + 255) / 256 doubles); *inertia (may be NULL with a
+ *   state) = their sum in block order; *bad is set to 1 (never cleared) if a best score is not finite.
+ *   With a state: MiniBatchKMeans._mini_batch_convergence with tol 0 on inertia / R, smoothing alpha;
+ *   max_no_improvement < 0 disables stopping.
+ * accumulate: sums[c] = the fp32 sum of the rows of Xb [R, d] whose code is c, added in row order;
+ *   cnt[c] = how many.  Nothing of size R x K is formed.
+ * update, one launch: where cnt[c] > 0, C[c] = (C[c] * counts[c] + sums[c]) / (counts[c] + cnt[c]) in
+ *   double and counts[c] += cnt[c]; then the images of C that mms2ut_kmeans_assign reads (c_hi, c_lo:
+ *   round_up(K, 16) rows, rows past K untouched; cnorm summed in double).  sums, cnt, counts NULL: the
+ *   images only.  *bad is set to 1 if a centre is not finite or exceeds fp16's range.
+ * pp: k-means++ over Xs [n, d] as sklearn's _kmeans_plusplus runs it.  Centre 0 is row `first`; for centre
+ *   c >= 1 the T candidates are the searchsorted (clipped to n - 1) of u[(c - 1) * T + t] * potential in the
+ *   double inclusive cumulative sum of the closest squared distances; the candidate with the lowest
+ *   potential is taken, the lowest t on a tie.  Distances are sum (x - y)^2 in fp32.  chosen int32 [K]: the
+ *   rows taken.  u: (K - 1) * T doubles on the device.  Workspaces: closest n floats, dist T * n floats,
+ *   partials ((n + MMS_KMEANS_PP_ROWS - 1) / MMS_KMEANS_PP_ROWS) * T doubles, cand T int32.  No host read.
+ * step: one mini-batch step over the rows idx int32 [R] of X: gather, assign, train_fold's fold, accumulate,
+ *   update, then the stopping rule.  The step that meets the rule keeps its update.                  */
+#define MMS_KMEANS_STATE 8
+#define MMS_KMEANS_PP_MAX_TRIALS 16
+#define MMS_KMEANS_PP_ROWS 16
+typedef struct {
+  const void* X;          /* fp16 [N, d], row stride ldx */
+  int64_t ldx, N;
+  const float* norms;     /* [N]: mms2ut_kmeans_row_norms */
+  int R, d, K, chunk;     /* batch rows, width, centroids, mms2ut_kmeans_chunks' chunk */
+  float* C;               /* fp32 [K, d] centres */
+  int64_t* counts;        /* [K] rows each centre has received */
+  void *c_hi, *c_lo;      /* fp16 [round_up(K, 16), d] */
+  float* cnorm;           /* [K] */
+  void* Xb;               /* workspaces: fp16 [R, d] */
+  float *xnorm_b, *pscore;/* [R]; [nchunks, R] */
+  int32_t *pidx, *code;   /* [nchunks, R]; [R] */
+  float* best;            /* [R] */
+  double* partials;       /* [(R + 255) / 256] */
+  float* sums;            /* [K, d] */
+  int32_t *cnt, *bad;     /* [K]; [1] */
+  double* state;          /* [MMS_KMEANS_STATE] */
+  double alpha;
+  int max_no_improvement; /* < 0: never stop early */
+} mms2ut_kmeans_step_args;
+int mms2ut_kmeans_row_norms(const void* X, int64_t ldx, int64_t R, int d, float* norms, hipStream_t stream);
+int mms2ut_kmeans_gather(const void* X, int64_t ldx, int64_t N, const float* norms, const int32_t* idx, int R, int d,
+                         void* out, int wide, float* norms_out, const double* state, hipStream_t stream);
+int mms2ut_kmeans_train_fold(const float* pscore, const int32_t* pidx, int nchunks, int R, const float* xnorm,
+                             int32_t* code, float* best, double* partials, double* inertia, int32_t* bad,
+                             double* state, double alpha, int max_no_improvement, hipStream_t stream);
+int mms2ut_kmeans_accumulate(const void* Xb, int64_t ldx, const int32_t* code, int R, int d, int K, float* sums,
+                             int32_t* cnt, const double* state, hipStream_t stream);
+int mms2ut_kmeans_update(float* C, int64_t* counts, const float* sums, const int32_t* cnt, int K, int d, void* c_hi,
+                         void* c_lo, float* cnorm, int32_t* bad, const double* state, hipStream_t stream);
+int mms2ut_kmeans_pp(const void* Xs, int n, int d, int K, int T, int first, const double* u, float* closest, float* dist,
+                     double* partials, int32_t* cand, int32_t* chosen, hipStream_t stream);
+int mms2ut_kmeans_step(const mms2ut_kmeans_step_args* args, const int32_t* idx, hipStream_t stream);
+
 /* ---------------------------------------------------------------- image front end (ViT features)
  * timm's eval transform of the vit_*_patch16_384 models on the device: torchvision Resize(S, bicubic) on
  * a PIL image, CenterCrop(S), ToTensor, Normalize, then the patch rows of the patch-embedding GEMM; one

@@ -187,6 +187,16 @@ class AsrConvArgs(C.Structure):
 ASR_CONV_ARGS = _packer(AsrConvArgs)
 HUBERT_GN_PARTS, KMEANS_LO_SCALE = 256, 2048              # include/mms2ut.h MMS_HUBERT_GN_PARTS, MMS_KMEANS_LO_SCALE
 
+KMEANS_STATE, KMEANS_PP_MAX_TRIALS, KMEANS_PP_ROWS = 8, 16, 16   # include/mms2ut.h MMS_KMEANS_STATE, MMS_KMEANS_PP_*
+
+
+class KMeansStepArgs(C.Structure):
+    """mms2ut_kmeans_step_args (include/mms2ut.h): the buffers of one mini-batch k-means step."""
+    _fields_ = [("X", vp), ("ldx", i64), ("N", i64), ("norms", vp), ("R", i32), ("d", i32), ("K", i32), ("chunk", i32)] + \
+        [(n, vp) for n in ("C", "counts", "c_hi", "c_lo", "cnorm", "Xb", "xnorm_b", "pscore", "pidx", "code", "best",
+                           "partials", "sums", "cnt", "bad", "state")] + [("alpha", C.c_double), ("max_no_improvement", i32)]
+
+
 VISION_TILE_BYTES, VISION_MAX_SIDE = 49152, 65535         # include/mms2ut.h MMS_VISION_*
 ROLLOUT_MAX_T = 640                                       # include/mms2ut.h MMS_ROLLOUT_MAX_T
 
@@ -308,6 +318,13 @@ SIGNATURES = {
     "mms2ut_kmeans_chunks": (i32, [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mms2ut_kmeans_assign": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "mms2ut_kmeans_fold": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "mms2ut_kmeans_row_norms": (i32, [vp, i64, i64, i32, vp, vp]),
+    "mms2ut_kmeans_gather": (i32, [vp, i64, i64, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "mms2ut_kmeans_train_fold": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32, vp]),
+    "mms2ut_kmeans_accumulate": (i32, [vp, i64, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "mms2ut_kmeans_update": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "mms2ut_kmeans_pp": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mms2ut_kmeans_step": (i32, [vp, vp, vp]),
     "mms2ut_vision_patches": (i32, [vp, i64, vp, i32, vp, i64, vp, vp, i32, i32, i32, vp]),
     "mms2ut_nonfinite_rows_f16": (i32, [vp, i64, i32, i64, vp, vp]),
     "mms2ut_rollout_probs_f16": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, f32, i32, vp, i64, vp]),

@@ -1839,6 +1839,181 @@ def kmeans_assign(X, c_hi, c_lo, cnorm, lens=None, *, chunk=None):
     return code, merged, count, bad
 
 
+# ============================================================================ unit codebook training (k-means)
+
+KMEANS_PP_MAX_TRIALS = _lib.KMEANS_PP_MAX_TRIALS
+
+
+def _km_rows(X, what):
+    _chk(X)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 8 or X.shape[1] % 8 or not X.is_contiguous():
+        raise ValueError(f"{what}: contiguous fp16 rows [N >= 1, d a multiple of 8] expected, got {tuple(X.shape)}")
+    return X.shape
+
+
+def kmeans_state(device):
+    """The device state of a fit (include/mms2ut.h MMS_KMEANS_STATE doubles), zeroed: steps run, EWA inertia,
+    its minimum, steps without improvement, done."""
+    return torch.zeros(_lib.KMEANS_STATE, dtype=torch.float64, device=device)
+
+
+def kmeans_row_norms(X):
+    """|x|^2 of fp16 rows X [N, d] -> fp32 [N]."""
+    N, d = _km_rows(X, "kmeans_row_norms")
+    norms = torch.empty(N, dtype=torch.float32, device=X.device)
+    call("mms2ut_kmeans_row_norms", X.data_ptr(), d, N, d, norms.data_ptr(), _s())
+    return norms
+
+
+def kmeans_gather(X, idx, norms=None, *, wide=False):
+    """Rows idx (int32 on the device, may repeat) of fp16 X [N, d] as a contiguous batch: fp16, or fp32 with
+    wide.  -> rows, or (rows, norms[idx]) given the rows' norms."""
+    N, d = _km_rows(X, "kmeans_gather")
+    _chk(idx, torch.int32)
+    if idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous():
+        raise ValueError("kmeans_gather: a contiguous index vector expected")
+    R = idx.numel()
+    out = torch.empty(R, d, dtype=torch.float32 if wide else F16, device=X.device)
+    nout = None
+    if norms is not None:
+        _f32c(norms, "kmeans_gather norms", N)
+        nout = torch.empty(R, dtype=torch.float32, device=X.device)
+    call("mms2ut_kmeans_gather", X.data_ptr(), d, N, _p(norms), idx.data_ptr(), R, d, out.data_ptr(), int(wide), _p(nout),
+         None, _s())
+    return out if norms is None else (out, nout)
+
+
+def kmeans_train_assign(X, xnorm, c_hi, c_lo, cnorm, *, chunk=None):
+    """The training side of kmeans_assign on fp16 rows X [R, d] with norms xnorm: -> (code int32 [R], best fp32
+    [R]: the best score cnorm - 2 x . C, inertia float64 [1]: the sum of max(|x|^2 + best, 0) in double in a
+    fixed order, bad int32 [1]: 1 if a best score is not finite).  No run merging, no utterances."""
+    R, d = _km_rows(X, "kmeans_train_assign")
+    _f32c(xnorm, "kmeans_train_assign xnorm", R)
+    _chk(c_hi)
+    _chk(c_lo)
+    Kc = cnorm.numel()
+    _f32c(cnorm, "kmeans_train_assign cnorm")
+    shape = (round_up(Kc, 16), d)
+    if Kc < 1 or tuple(c_hi.shape) != shape or tuple(c_lo.shape) != shape or not (c_hi.is_contiguous() and c_lo.is_contiguous()):
+        raise ValueError(f"kmeans_train_assign: {Kc} centroids of width {d} need contiguous images {shape}")
+    dev = X.device
+    chunk, nchunks = kmeans_chunks(R, Kc, chunk)
+    pscore = torch.empty(nchunks, R, dtype=torch.float32, device=dev)
+    pidx = torch.empty(nchunks, R, dtype=torch.int32, device=dev)
+    code = torch.empty(R, dtype=torch.int32, device=dev)
+    best = torch.empty(R, dtype=torch.float32, device=dev)
+    partials = torch.empty((R + 255) // 256, dtype=torch.float64, device=dev)
+    inertia = torch.empty(1, dtype=torch.float64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("mms2ut_kmeans_assign", X.data_ptr(), d, R, d, c_hi.data_ptr(), c_lo.data_ptr(), cnorm.data_ptr(), Kc, chunk,
+         pscore.data_ptr(), pidx.data_ptr(), _s())
+    call("mms2ut_kmeans_train_fold", pscore.data_ptr(), pidx.data_ptr(), nchunks, R, xnorm.data_ptr(), code.data_ptr(),
+         best.data_ptr(), partials.data_ptr(), inertia.data_ptr(), bad.data_ptr(), None, 0.0, -1, _s())
+    return code, best, inertia, bad
+
+
+def kmeans_accumulate(Xb, code, Kc):
+    """(sums fp32 [Kc, d], cnt int32 [Kc]): per centroid the sum of the rows of fp16 Xb [R, d] whose code it is,
+    added in row order in fp32, and their number.  Bitwise reproducible; no [R, Kc] array is formed."""
+    R, d = _km_rows(Xb, "kmeans_accumulate")
+    _chk(code, torch.int32)
+    if code.numel() != R or not code.is_contiguous() or Kc < 1:
+        raise ValueError(f"kmeans_accumulate: {R} codes and Kc >= 1 expected")
+    sums = torch.empty(Kc, d, dtype=torch.float32, device=Xb.device)
+    cnt = torch.empty(Kc, dtype=torch.int32, device=Xb.device)
+    call("mms2ut_kmeans_accumulate", Xb.data_ptr(), d, code.data_ptr(), R, d, int(Kc), sums.data_ptr(), cnt.data_ptr(), None,
+         _s())
+    return sums, cnt
+
+
+def kmeans_images(Kc, d, device):
+    """Zeroed (c_hi, c_lo, cnorm) for kmeans_update to fill."""
+    return (torch.zeros(round_up(Kc, 16), d, dtype=F16, device=device), torch.zeros(round_up(Kc, 16), d, dtype=F16, device=device),
+            torch.zeros(Kc, dtype=torch.float32, device=device))
+
+
+def kmeans_update(C, images, bad, counts=None, sums=None, cnt=None):
+    """In place, one launch and no host read: where cnt > 0 the centre becomes (C * counts + sums) / (counts +
+    cnt) and counts grows by cnt; then kmeans_pack's images of C into images = (c_hi, c_lo, cnorm).  Without
+    counts / sums / cnt: the images only.  bad int32 [1] is set where a centre is not finite or outside
+    fp16's range.  C fp32 [Kc, d], counts int64 [Kc]."""
+    _chk(C, torch.float32)
+    if C.dim() != 2 or not C.is_contiguous() or C.shape[1] % 8 or C.shape[1] < 8:
+        raise ValueError(f"kmeans_update: contiguous centres [Kc, d a multiple of 8] expected, got {tuple(C.shape)}")
+    Kc, d = C.shape
+    hi, lo, cn = images
+    _chk(hi)
+    _chk(lo)
+    _f32c(cn, "kmeans_update cnorm", Kc)
+    _chk(bad, torch.int32)
+    shape = (round_up(Kc, 16), d)
+    if tuple(hi.shape) != shape or tuple(lo.shape) != shape or not (hi.is_contiguous() and lo.is_contiguous()):
+        raise ValueError(f"kmeans_update: contiguous images {shape} expected")
+    if (counts is None) != (sums is None) or (counts is None) != (cnt is None):
+        raise ValueError("kmeans_update: counts, sums and cnt go together")
+    if counts is not None:
+        _chk(counts, torch.int64)
+        _chk(cnt, torch.int32)
+        _f32c(sums, "kmeans_update sums", Kc * d)
+        assert counts.is_contiguous() and cnt.is_contiguous() and counts.numel() == Kc and cnt.numel() == Kc
+    call("mms2ut_kmeans_update", C.data_ptr(), _p(counts), _p(sums), _p(cnt), Kc, d, hi.data_ptr(), lo.data_ptr(), cn.data_ptr(),
+         bad.data_ptr(), None, _s())
+
+
+def kmeans_pp(Xs, Kc, first, u):
+    """k-means++ seeding over fp16 rows Xs [n, d] (csrc/kmeans.hip): row `first` is centre 0; u float64 [Kc - 1,
+    trials] on the device are the uniforms of the other centres' candidates.  -> chosen int32 [Kc] (rows of
+    Xs), without a host read."""
+    n, d = _km_rows(Xs, "kmeans_pp")
+    dev = Xs.device
+    _chk(u, torch.float64)
+    if u.dim() != 2 or u.shape[0] != Kc - 1 or not 1 <= u.shape[1] <= KMEANS_PP_MAX_TRIALS or not u.is_contiguous():
+        raise ValueError(f"kmeans_pp: uniforms [Kc - 1, 1 .. {KMEANS_PP_MAX_TRIALS} trials] expected, got {tuple(u.shape)}")
+    if not 0 <= first < n:
+        raise ValueError(f"kmeans_pp: first row {first} outside [0, {n})")
+    T = u.shape[1]
+    closest = torch.empty(n, dtype=torch.float32, device=dev)
+    dist = torch.empty(T, n, dtype=torch.float32, device=dev)
+    partials = torch.empty(-(-n // _lib.KMEANS_PP_ROWS), T, dtype=torch.float64, device=dev)
+    cand = torch.zeros(T, dtype=torch.int32, device=dev)
+    chosen = torch.empty(Kc, dtype=torch.int32, device=dev)
+    call("mms2ut_kmeans_pp", Xs.data_ptr(), n, d, int(Kc), T, int(first), u.data_ptr(), closest.data_ptr(), dist.data_ptr(),
+         partials.data_ptr(), cand.data_ptr(), chosen.data_ptr(), _s())
+    return chosen
+
+
+class KMeansStep:
+    """The buffers of a fit's mini-batch steps (mms2ut_kmeans_step_args) and the call that runs one.  X fp16 [N, d]
+    with norms; C fp32 [Kc, d] (updated in place); R rows per batch.  counts, images, bad and state are made
+    here: state's layout is kmeans_state's."""
+
+    def __init__(self, X, norms, C, R, alpha, max_no_improvement):
+        N, d = _km_rows(X, "KMeansStep")
+        _f32c(norms, "KMeansStep norms", N)
+        _chk(C, torch.float32)
+        assert C.is_contiguous() and C.dim() == 2 and C.shape[1] == d
+        Kc, dev = C.shape[0], X.device
+        chunk, nchunks = kmeans_chunks(R, Kc)
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
+        self.counts, self.images, self.bad, self.state = z(Kc, dt=torch.int64), kmeans_images(Kc, d, dev), \
+            z(1, dt=torch.int32), kmeans_state(dev)
+        self.ws = (z(R, d, dt=F16), z(R), z(nchunks, R), z(nchunks, R, dt=torch.int32), z(R, dt=torch.int32), z(R),
+                   z((R + 255) // 256, dt=torch.float64), z(Kc, d), z(Kc, dt=torch.int32))
+        self.keep = (X, norms, C)
+        kmeans_update(C, self.images, self.bad)
+        hi, lo, cn = self.images
+        self.args = _lib.KMeansStepArgs(
+            X.data_ptr(), d, N, norms.data_ptr(), int(R), d, Kc, chunk, C.data_ptr(), self.counts.data_ptr(), hi.data_ptr(),
+            lo.data_ptr(), cn.data_ptr(), *(t.data_ptr() for t in self.ws), self.bad.data_ptr(), self.state.data_ptr(),
+            float(alpha), -1 if max_no_improvement is None else int(max_no_improvement))
+        self.ref = ctypes.byref(self.args)
+        self.R = int(R)
+
+    def __call__(self, idx):
+        """One step on the rows idx (int32 [R] on the device); nothing is read back."""
+        call("mms2ut_kmeans_step", self.ref, idx.data_ptr(), _s())
+
+
 # ============================================================================ image front end (ViT features)
 
 VISION_TILE_BYTES, VISION_MAX_SIDE = _lib.VISION_TILE_BYTES, _lib.VISION_MAX_SIDE

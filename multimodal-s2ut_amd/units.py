@@ -81,7 +81,8 @@ def merge(code):
 
 
 class HubertUnits(SpeechEncoder):
-    """HF HubertModel in eval mode up to hidden_states[km_layer], then nearest-centroid units."""
+    """HF HubertModel in eval mode up to hidden_states[km_layer], then nearest-centroid units (centroids None:
+    the features only)."""
 
     def __init__(self, state_dict, config, centroids, km_layer=11, preprocessor_cfg=None, device="cuda"):
         c = parse_config(config)
@@ -89,19 +90,24 @@ class HubertUnits(SpeechEncoder):
         pre = dict(preprocessor_cfg or {})
         self.normalize = bool(pre.get("do_normalize", False))   # no preprocessor config: the samples as they are
         w = Weights(fold_pos_conv_weight_norm(strip_prefix(state_dict), ""), "hubert checkpoint", device)
-        Cm = torch.as_tensor(np.asarray(centroids), dtype=torch.float32)
-        if Cm.dim() != 2 or Cm.shape[1] != c["hidden_size"]:
-            raise ValueError(f"centroids of shape {tuple(Cm.shape)} do not match the model's feature width "
-                             f"{c['hidden_size']}")
-        self.n_units = Cm.shape[0]
-        self.c_hi, self.c_lo, self.c_norm = K.kmeans_pack(Cm.to(w.device))
+        if centroids is None:                                   # features only (kmeans.py trains the codebook from them)
+            self.n_units, self.c_hi, self.c_lo, self.c_norm = 0, None, None, None
+        else:
+            Cm = torch.as_tensor(np.asarray(centroids), dtype=torch.float32)
+            if Cm.dim() != 2 or Cm.shape[1] != c["hidden_size"]:
+                raise ValueError(f"centroids of shape {tuple(Cm.shape)} do not match the model's feature width "
+                                 f"{c['hidden_size']}")
+            self.n_units = Cm.shape[0]
+            self.c_hi, self.c_lo, self.c_norm = K.kmeans_pack(Cm.to(w.device))
         # the layers past km_layer are neither loaded nor run
         super().__init__(w, c, "", self.km_layer, pre.get("sampling_rate", SAMPLE_RATE))
 
     @classmethod
     def from_pretrained(cls, model_dir, km_path, km_layer=11, device="cuda"):
-        return cls(load_state_dict(model_dir), read_json(model_dir, "config.json", True), load_centroids(km_path),
-                   km_layer, read_json(model_dir, "preprocessor_config.json"), device)
+        """km_path None: no centroids, features only (features, features_batch)."""
+        return cls(load_state_dict(model_dir), read_json(model_dir, "config.json", True),
+                   None if km_path is None else load_centroids(km_path), km_layer,
+                   read_json(model_dir, "preprocessor_config.json"), device)
 
     # ---------------------------------------------------------------------------------- forward
 
@@ -133,6 +139,8 @@ class HubertUnits(SpeechEncoder):
 
     def forward_batch(self, waves, sr=None):
         """Waveforms -> (features, lens, code, merged, count, bad: kernels.kmeans_assign's results)."""
+        if self.c_hi is None:
+            raise RuntimeError("this HubertUnits was loaded without centroids: it extracts features only")
         Fb, lens, lens32 = self.features_batch(waves, sr)
         return (Fb, lens) + K.kmeans_assign(Fb, self.c_hi, self.c_lo, self.c_norm, lens32)
 
