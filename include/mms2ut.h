@@ -819,6 +819,40 @@ int mms2ut_kmeans_assign(const void* X, int64_t ldx, int R, int d, const void* c
                          const float* cnorm, int Kc, int chunk, float* pscore, int32_t* pidx, hipStream_t stream);
 int mms2ut_kmeans_fold(const float* pscore, const int32_t* pidx, int nchunks, int B, int Tmax, const int32_t* lens,
                        int32_t* code, int32_t* merged, int32_t* count, int32_t* bad, hipStream_t stream);
+/* The top_k nearest centroids (1 <= top_k <= min(MMS_KMEANS_TOPK_MAX, Kc)): mms2ut_kmeans_assign's inputs,
+ * chunks and score, with the top_k smallest (score, index) pairs per row ordered by (score, index), so the
+ * first is mms2ut_kmeans_assign's choice.  Chunk ch writes its list of row r to pscore / pidx
+ * [(ch * R + r) * top_k ...].  mms2ut_kmeans_topk_fold merges the chunks' lists of the frames t < lens[b]
+ * (or Tmax) of a packed batch: idx[b, t, 0..top_k) and dist[b, t, j] = sqrt(max(xnorm + score, 0)), the
+ * correctly rounded Euclidean distance, xnorm fp32 [B * Tmax] = mms2ut_kmeans_row_norms of X.  Other rows
+ * are not written.  bad int32 [B], ZEROED by the caller: set to 1 where a frame has a score, norm or
+ * distance that is not finite, or top_k distances that are all 0.                                    */
+#define MMS_KMEANS_TOPK_MAX 32
+int mms2ut_kmeans_topk(const void* X, int64_t ldx, int R, int d, const void* c_hi, const void* c_lo,
+                       const float* cnorm, int Kc, int chunk, int top_k, float* pscore, int32_t* pidx,
+                       hipStream_t stream);
+int mms2ut_kmeans_topk_fold(const float* pscore, const int32_t* pidx, int nchunks, int B, int Tmax,
+                            const int32_t* lens, const float* xnorm, int top_k, int32_t* idx, float* dist,
+                            int32_t* bad, hipStream_t stream);
+/* Length-penalised beam search over the frames' top_k candidates -- csrc/units_beam.hip, the float32
+ * evaluation of the reference's mhubert.py HubertCode.decode(beamsearch=True).  idx int32, dist fp32
+ * [B, Tmax, top_k] (mms2ut_kmeans_topk_fold's), T = lens[b] (or Tmax) frames per utterance, one block each.
+ * A kept sequence carries (score, runs, last token), at first one empty sequence of score 1.  Frame t's
+ * candidate seq * top_k + j appends idx[t, j]; its score is
+ *   f32(score + f32(f32(m / T) * f32(dist[t, j] / s)))
+ * with m the candidate's run count, m / T formed in double, s the sum of the frame's top_k distances in
+ * numpy's pairwise order; every operation rounds on its own.  The beamsize candidates of lowest (score,
+ * candidate index) are kept in that order.  beam_code[b, 0..T) = the first kept sequence after the last
+ * frame, merged[b, 0..count[b]) = its runs collapsed; bad[b] = 1 where a frame's s is 0 or not finite
+ * (the other outputs of b then mean nothing).  ws: mms2ut_units_beam_ws bytes, holding the (parent,
+ * token) back-pointers [B, Tmax, beamsize].  Integer and fp32 work only, no atomics: every run gives the
+ * same bits.  Limits: 1 <= top_k <= MMS_KMEANS_TOPK_MAX, beamsize >= 1, beamsize * top_k <=
+ * MMS_UNITS_BEAM_MAX_CAND.                                                                            */
+#define MMS_UNITS_BEAM_MAX_CAND 2048
+int mms2ut_units_beam_ws(int B, int Tmax, int beamsize, int64_t* bytes);
+int mms2ut_units_beam(const int32_t* idx, const float* dist, int B, int Tmax, const int32_t* lens, int top_k,
+                      int beamsize, void* ws, int32_t* beam_code, int32_t* merged, int32_t* count, int32_t* bad,
+                      hipStream_t stream);
 
 /* ---------------------------------------------------------------- unit codebook training (k-means)
  * scikit-learn's MiniBatchKMeans.fit on fp16 rows X [N, d] (d a multiple of 8, 16-byte aligned rows) --

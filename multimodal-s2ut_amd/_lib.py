@@ -186,6 +186,7 @@ class AsrConvArgs(C.Structure):
 
 ASR_CONV_ARGS = _packer(AsrConvArgs)
 HUBERT_GN_PARTS, KMEANS_LO_SCALE = 256, 2048              # include/mms2ut.h MMS_HUBERT_GN_PARTS, MMS_KMEANS_LO_SCALE
+KMEANS_TOPK_MAX, UNITS_BEAM_MAX_CAND = 32, 2048           # include/mms2ut.h MMS_KMEANS_TOPK_MAX, MMS_UNITS_BEAM_MAX_CAND
 
 KMEANS_STATE, KMEANS_PP_MAX_TRIALS, KMEANS_PP_ROWS = 8, 16, 16   # include/mms2ut.h MMS_KMEANS_STATE, MMS_KMEANS_PP_*
 
@@ -318,6 +319,10 @@ SIGNATURES = {
     "mms2ut_kmeans_chunks": (i32, [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mms2ut_kmeans_assign": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "mms2ut_kmeans_fold": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "mms2ut_kmeans_topk": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "mms2ut_kmeans_topk_fold": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]),
+    "mms2ut_units_beam_ws": (i32, [i32, i32, i32, C.POINTER(i64)]),
+    "mms2ut_units_beam": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mms2ut_kmeans_row_norms": (i32, [vp, i64, i64, i32, vp, vp]),
     "mms2ut_kmeans_gather": (i32, [vp, i64, i64, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
     "mms2ut_kmeans_train_fold": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32, vp]),

@@ -21,6 +21,11 @@
 //   kmeans_fold        one block per utterance: folds the chunk partials in chunk order (the lowest
 //                      index wins a tie), writes the per-frame codes, compacts the run starts
 //                      (ctc_greedy's scan without a blank) and flags a non-finite best score.
+//   kmeans_topk        kmeans_assign's GEMM and score with the top_k <= 32 smallest (score, index) pairs per
+//                      row kept in LDS, ordered by (score, index): the first pair is kmeans_assign's choice
+//                      bit for bit.  Per chunk a list of top_k pairs per row goes to a workspace.
+//   kmeans_topk_fold   one thread per frame: merges the chunks' lists and writes the indices and the
+//                      Euclidean distances sqrt(max(|x|^2 + score, 0)), the input of units_beam.hip.
 #include "common.h"
 #include "../../include/mms2ut.h"
 
@@ -165,6 +170,39 @@ constexpr float KM_LO_SCALE = 1.f / (float)MMS_KMEANS_LO_SCALE;
 
 MMS_DEV bool km_better(float s, int i, float bs, int bi) { return s < bs || (s == bs && i < bi); }
 
+// one pass of a wave: the hi and lo products of its 16 rows of X with the nt tiles of 16 centroids from c0
+MMS_DEV void km_pass(const h16* __restrict__ xr, bool rv, int d, const h16* __restrict__ Chi, const h16* __restrict__ Clo,
+                     int c0, int nt, int l15, int lk, f32x4 (&ah)[KM_NT], f32x4 (&al)[KM_NT]) {
+  const int nsteps = (d + 31) >> 5;
+#pragma unroll
+  for (int t = 0; t < KM_NT; ++t) ah[t] = al[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < nsteps; ++s) {
+    const int kk = s * 32 + lk;
+    const bool kv = kk < d;                               // d is a multiple of 8: whole pieces
+    h16x8 xf = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rv && kv) xf = *reinterpret_cast<const h16x8*>(xr + kk);
+    h16x8 hf[KM_NT], lf[KM_NT];
+#pragma unroll
+    for (int t = 0; t < KM_NT; ++t) {
+      hf[t] = lf[t] = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (t < nt && kv) {                                 // rows < round_up(Kc, 16): inside the images
+        const long off = (long)(c0 + t * 16 + l15) * d + kk;
+        hf[t] = *reinterpret_cast<const h16x8*>(Chi + off);
+        lf[t] = *reinterpret_cast<const h16x8*>(Clo + off);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < KM_NT; ++t)
+      if (t < nt) {
+        ah[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[t], xf, ah[t], 0, 0, 0);
+        al[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(lf[t], xf, al[t], 0, 0, 0);
+      }
+  }
+}
+
+// centroid c's score from its accumulators: |C_c|^2 - 2 (x.hi + x.lo / 2^11)
+MMS_DEV float km_score(float hi, float lo, float cn) { return fmaf(-2.f, fmaf(lo, KM_LO_SCALE, hi), cn); }
+
 __global__ void __launch_bounds__(KM_THREADS) kmeans_assign_kernel(
     const h16* __restrict__ X, long ldx, int R, int d, const h16* __restrict__ Chi, const h16* __restrict__ Clo,
     const float* __restrict__ cn, int Kc, int chunk, float* __restrict__ pscore, int* __restrict__ pidx) {
@@ -176,36 +214,12 @@ __global__ void __launch_bounds__(KM_THREADS) kmeans_assign_kernel(
   const bool rv = r < R;
   const h16* __restrict__ xr = X + (long)(rv ? r : 0) * ldx;
   const int cbeg = blockIdx.y * chunk, cend = min(Kc, cbeg + chunk);
-  const int nsteps = (d + 31) >> 5;
   float best = INFINITY;
   int bi = INT_MAX;
   for (int c0 = cbeg; c0 < cend; c0 += KM_PASS) {
     const int nt = min(KM_NT, (cend - c0 + 15) >> 4);     // tiles that hold a real centroid
     f32x4 ah[KM_NT], al[KM_NT];
-#pragma unroll
-    for (int t = 0; t < KM_NT; ++t) ah[t] = al[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < nsteps; ++s) {
-      const int kk = s * 32 + lk;
-      const bool kv = kk < d;                             // d is a multiple of 8: whole pieces
-      h16x8 xf = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (rv && kv) xf = *reinterpret_cast<const h16x8*>(xr + kk);
-      h16x8 hf[KM_NT], lf[KM_NT];
-#pragma unroll
-      for (int t = 0; t < KM_NT; ++t) {
-        hf[t] = lf[t] = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (t < nt && kv) {                               // rows < round_up(Kc, 16): inside the images
-          const long off = (long)(c0 + t * 16 + l15) * d + kk;
-          hf[t] = *reinterpret_cast<const h16x8*>(Chi + off);
-          lf[t] = *reinterpret_cast<const h16x8*>(Clo + off);
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < KM_NT; ++t)
-        if (t < nt) {
-          ah[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[t], xf, ah[t], 0, 0, 0);
-          al[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(lf[t], xf, al[t], 0, 0, 0);
-        }
-    }
+    km_pass(xr, rv, d, Chi, Clo, c0, nt, l15, lk, ah, al);
     // D[row = centroid (lane>>4)*4 + e][col = row of X lane&15]: ascending centroids within a lane
 #pragma unroll
     for (int t = 0; t < KM_NT; ++t) {
@@ -214,7 +228,7 @@ __global__ void __launch_bounds__(KM_THREADS) kmeans_assign_kernel(
       for (int e = 0; e < 4; ++e) {
         const int c = c0 + t * 16 + (lane >> 4) * 4 + e;
         if (c >= cend) continue;                          // the padded centroids take no part
-        const float sc = fmaf(-2.f, fmaf(al[t][e], KM_LO_SCALE, ah[t][e]), cn[c]);
+        const float sc = km_score(ah[t][e], al[t][e], cn[c]);
         if (sc < best) {                                  // strict: the lowest index wins a tie
           best = sc;
           bi = c;
@@ -296,6 +310,119 @@ __global__ void __launch_bounds__(KF_THREADS) kmeans_fold_kernel(
   if (tid == 0) count[b] = base;
 }
 
+// ---------------------------------------------------------------------------------------------
+// the top_k nearest centroids
+// ---------------------------------------------------------------------------------------------
+constexpr int KT_MAX = MMS_KMEANS_TOPK_MAX;
+constexpr int KT_LD = KT_MAX + 1;                         // a row's list in LDS: odd stride, rows on distinct banks
+constexpr int KTF_THREADS = 64;
+
+// A row's list: k (score, index) pairs ascending by (score, index), (inf, INT_MAX) where empty.  (s, i)
+// enters if it is better than the last pair; a NaN never does.  One lane per list at a time.
+MMS_DEV void kt_insert(volatile float* ls, volatile int* li, int k, float s, int i) {
+  if (!km_better(s, i, ls[k - 1], li[k - 1])) return;
+  int j = k - 1;
+  while (j > 0 && km_better(s, i, ls[j - 1], li[j - 1])) {
+    ls[j] = ls[j - 1];
+    li[j] = li[j - 1];
+    --j;
+  }
+  ls[j] = s;
+  li[j] = i;
+}
+
+// kmeans_assign_kernel with a list of k per row in place of the one best.  A wave touches only the lists
+// of its own 16 rows, so the kernel has no block barrier; the four lanes that share a row take turns.
+__global__ void __launch_bounds__(KM_THREADS) kmeans_topk_kernel(
+    const h16* __restrict__ X, long ldx, int R, int d, const h16* __restrict__ Chi, const h16* __restrict__ Clo,
+    const float* __restrict__ cn, int Kc, int chunk, int k, float* __restrict__ pscore, int* __restrict__ pidx) {
+  __shared__ float ls[KM_ROWS * KT_LD];
+  __shared__ int li[KM_ROWS * KT_LD];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l15 = lane & 15, lk = (lane >> 4) * 8, grp = lane >> 4;
+  const int r0 = blockIdx.x * KM_ROWS + wave * 16;
+  if (r0 >= R) return;                                    // wave-uniform
+  const int r = r0 + l15;
+  const bool rv = r < R;
+  const h16* __restrict__ xr = X + (long)(rv ? r : 0) * ldx;
+  const int cbeg = blockIdx.y * chunk, cend = min(Kc, cbeg + chunk);
+  volatile float* ms = ls + (wave * 16 + l15) * KT_LD;
+  volatile int* mi = li + (wave * 16 + l15) * KT_LD;
+  for (int j = grp; j < k; j += 4) {
+    ms[j] = INFINITY;
+    mi[j] = INT_MAX;
+  }
+  for (int c0 = cbeg; c0 < cend; c0 += KM_PASS) {
+    const int nt = min(KM_NT, (cend - c0 + 15) >> 4);
+    f32x4 ah[KM_NT], al[KM_NT];
+    km_pass(xr, rv, d, Chi, Clo, c0, nt, l15, lk, ah, al);
+    for (int g = 0; g < 4; ++g) {
+      __builtin_amdgcn_wave_barrier();                    // LDS operations of a wave complete in order
+      if (grp != g) continue;
+#pragma unroll
+      for (int t = 0; t < KM_NT; ++t) {
+        if (t >= nt) continue;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = c0 + t * 16 + grp * 4 + e;
+          if (c < cend) kt_insert(ms, mi, k, km_score(ah[t][e], al[t][e], cn[c]), c);
+        }
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (rv)
+    for (int j = grp; j < k; j += 4) {
+      const long o = ((long)blockIdx.y * R + r) * k + j;
+      pscore[o] = ms[j];
+      pidx[o] = mi[j];
+    }
+}
+
+// One thread per frame of utterance blockIdx.y: merges the chunks' lists (each ascending, so a chunk is
+// left at its first pair that does not enter), then dist = sqrt(max(|x|^2 + score, 0)).  bad[b] (zeroed by
+// the caller) is set where a kept score, a norm or a distance is not finite, a list is short of k
+// comparable scores, or the k distances are all 0 (their sum is the beam's divisor).
+__global__ void __launch_bounds__(KTF_THREADS) kmeans_topk_fold_kernel(
+    const float* __restrict__ pscore, const int* __restrict__ pidx, int nchunks, long R, int Tmax,
+    const int* __restrict__ lens, const float* __restrict__ xnorm, int k, int* __restrict__ idx,
+    float* __restrict__ dist, int* __restrict__ bad) {
+  __shared__ float ls[KTF_THREADS * KT_LD];
+  __shared__ int li[KTF_THREADS * KT_LD];
+  const int b = blockIdx.y, t = blockIdx.x * KTF_THREADS + threadIdx.x;
+  const int T = lens ? min(max(lens[b], 0), Tmax) : Tmax;
+  if (t >= T) return;                                     // no barrier in this kernel
+  const long row = (long)b * Tmax + t;
+  volatile float* ms = ls + threadIdx.x * KT_LD;
+  volatile int* mi = li + threadIdx.x * KT_LD;
+  for (int j = 0; j < k; ++j) {
+    ms[j] = INFINITY;
+    mi[j] = INT_MAX;
+  }
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const long o = ((long)ch * R + row) * k;
+    for (int j = 0; j < k; ++j) {
+      const float s = pscore[o + j];
+      const int i = pidx[o + j];
+      if (!km_better(s, i, ms[k - 1], mi[k - 1])) break;
+      kt_insert(ms, mi, k, s, i);
+    }
+  }
+  const float xn = xnorm[row];
+  int notfin = isfinite(xn) ? 0 : 1;
+  float last = 0.f;
+  for (int j = 0; j < k; ++j) {
+    const float s = ms[j];
+    const int i = mi[j];
+    const float v = xn + s;
+    if (!isfinite(s) || !isfinite(v)) notfin = 1;
+    last = v > 0.f ? (float)sqrt((double)v) : 0.f;        // correctly rounded: the double root carries 53 bits
+    idx[row * k + j] = i == INT_MAX ? 0 : i;
+    dist[row * k + j] = last;
+  }
+  if (notfin || last == 0.f) bad[b] = 1;                  // every writer stores the same value
+}
+
 }  // namespace
 
 extern "C" int mms2ut_hubert_conv0(const float* x, int64_t n, const float* stats, const float* w, const float* bias,
@@ -349,6 +476,39 @@ extern "C" int mms2ut_kmeans_assign(const void* X, int64_t ldx, int R, int d, co
                      reinterpret_cast<const h16*>(X), (long)ldx, R, d, reinterpret_cast<const h16*>(c_hi),
                      reinterpret_cast<const h16*>(c_lo), cnorm, Kc, chunk, pscore, pidx);
   return mms::check_launch("kmeans_assign");
+}
+
+extern "C" int mms2ut_kmeans_topk(const void* X, int64_t ldx, int R, int d, const void* c_hi, const void* c_lo,
+                                  const float* cnorm, int Kc, int chunk, int top_k, float* pscore, int32_t* pidx,
+                                  hipStream_t s) {
+  MMS_REQUIRE(X && c_hi && c_lo && cnorm && pscore && pidx, "kmeans_topk: null buffer");
+  MMS_REQUIRE(R >= 1 && Kc >= 1, "kmeans_topk: R %d, Kc %d", R, Kc);
+  MMS_REQUIRE(top_k >= 1 && top_k <= KT_MAX && top_k <= Kc, "kmeans_topk: top_k must be in [1, min(%d, Kc = %d)] (got %d)",
+              KT_MAX, Kc, top_k);
+  MMS_REQUIRE(d >= 8 && d % 8 == 0 && ldx >= d && ldx % 8 == 0, "kmeans_topk: d must be a multiple of 8 with 16-byte "
+              "aligned rows (d %d, ldx %ld)", d, (long)ldx);
+  MMS_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)c_hi & 15) == 0 && ((uintptr_t)c_lo & 15) == 0,
+              "kmeans_topk: misaligned buffer");
+  MMS_REQUIRE(chunk >= KM_PASS && chunk % KM_PASS == 0, "kmeans_topk: chunk must be a positive multiple of %d (got %d)",
+              KM_PASS, chunk);
+  const long nchunks = ((long)Kc + chunk - 1) / chunk;
+  MMS_REQUIRE(nchunks <= 65535, "kmeans_topk: %ld chunks", nchunks);
+  hipLaunchKernelGGL(kmeans_topk_kernel, dim3((R + KM_ROWS - 1) / KM_ROWS, (unsigned)nchunks), dim3(KM_THREADS), 0, s,
+                     reinterpret_cast<const h16*>(X), (long)ldx, R, d, reinterpret_cast<const h16*>(c_hi),
+                     reinterpret_cast<const h16*>(c_lo), cnorm, Kc, chunk, top_k, pscore, pidx);
+  return mms::check_launch("kmeans_topk");
+}
+
+extern "C" int mms2ut_kmeans_topk_fold(const float* pscore, const int32_t* pidx, int nchunks, int B, int Tmax,
+                                       const int32_t* lens, const float* xnorm, int top_k, int32_t* idx, float* dist,
+                                       int32_t* bad, hipStream_t s) {
+  MMS_REQUIRE(pscore && pidx && xnorm && idx && dist && bad, "kmeans_topk_fold: null buffer");
+  MMS_REQUIRE(nchunks >= 1 && B >= 1 && B <= 65535 && Tmax >= 1 && (long)B * Tmax < (1L << 31),
+              "kmeans_topk_fold: nchunks %d, B %d, Tmax %d", nchunks, B, Tmax);
+  MMS_REQUIRE(top_k >= 1 && top_k <= KT_MAX, "kmeans_topk_fold: top_k must be in [1, %d] (got %d)", KT_MAX, top_k);
+  hipLaunchKernelGGL(kmeans_topk_fold_kernel, dim3((Tmax + KTF_THREADS - 1) / KTF_THREADS, B), dim3(KTF_THREADS), 0, s,
+                     pscore, pidx, nchunks, (long)B * Tmax, Tmax, lens, xnorm, top_k, idx, dist, bad);
+  return mms::check_launch("kmeans_topk_fold");
 }
 
 extern "C" int mms2ut_kmeans_fold(const float* pscore, const int32_t* pidx, int nchunks, int B, int Tmax,

@@ -1839,6 +1839,97 @@ def kmeans_assign(X, c_hi, c_lo, cnorm, lens=None, *, chunk=None):
     return code, merged, count, bad
 
 
+KMEANS_TOPK_MAX, UNITS_BEAM_MAX_CAND = _lib.KMEANS_TOPK_MAX, _lib.UNITS_BEAM_MAX_CAND
+
+
+def check_beam_limits(top_k, beamsize=1):
+    """The limits of kmeans_topk and units_beam (include/mms2ut.h), checked before anything runs."""
+    top_k, beamsize = int(top_k), int(beamsize)
+    if top_k < 1 or beamsize < 1:
+        raise ValueError(f"top_k and beamsize must be >= 1 (got {top_k}, {beamsize})")
+    if top_k > KMEANS_TOPK_MAX:
+        raise NotImplementedError(f"top_k {top_k} exceeds the limit of {KMEANS_TOPK_MAX} candidates per frame")
+    if beamsize * top_k > UNITS_BEAM_MAX_CAND:
+        raise NotImplementedError(f"beamsize {beamsize} x top_k {top_k} exceeds the limit of {UNITS_BEAM_MAX_CAND} "
+                                  "candidates per frame")
+    return top_k, beamsize
+
+
+def kmeans_topk(X, c_hi, c_lo, cnorm, lens=None, *, top_k=10, chunk=None):
+    """The top_k nearest centroids of every frame of fp16 X [B, Tmax, d] (or [T, d]) against kmeans_pack's
+    images, in kmeans_assign's GEMM with the top_k smallest (score, index) pairs per row kept on chip; no
+    [rows, centroids] matrix is written.  -> (idx int32 [B, Tmax, top_k] ascending by (distance, index), so
+    idx[..., 0] is kmeans_assign's code bit for bit; dist fp32 [B, Tmax, top_k] = sqrt(max(|x|^2 + score, 0)),
+    the Euclidean distances; bad int32 [B]: 1 where a frame has a non-finite distance or top_k distances
+    that sum to 0).  Rows past lens[b] hold zeros.  1 <= top_k <= min(32, Kc)."""
+    _chk(X)
+    if X.dim() == 2:
+        X = X.unsqueeze(0)
+    if X.dim() != 3 or not X.is_contiguous() or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"kmeans_topk: contiguous X [B, Tmax, d] expected, got {tuple(X.shape)}")
+    B, Tmax, d = X.shape
+    _chk(c_hi)
+    _chk(c_lo)
+    Kc = cnorm.numel()
+    _f32c(cnorm, "kmeans_topk cnorm")
+    shape = (round_up(Kc, 16), d)
+    if Kc < 1 or tuple(c_hi.shape) != shape or tuple(c_lo.shape) != shape or not c_hi.is_contiguous() \
+            or not c_lo.is_contiguous():
+        raise ValueError(f"kmeans_topk: centroid images {tuple(c_hi.shape)}, {tuple(c_lo.shape)}; {Kc} centroids of "
+                         f"width {d} need contiguous {shape} (kmeans_pack)")
+    top_k, _ = check_beam_limits(top_k)
+    if top_k > Kc:
+        raise ValueError(f"kmeans_topk: top_k {top_k} exceeds the {Kc} centroids")
+    if lens is not None:
+        _chk(lens, torch.int32)
+        assert lens.is_contiguous() and lens.numel() == B
+    R, dev = B * Tmax, X.device
+    chunk, nchunks = kmeans_chunks(R, Kc, chunk)
+    pscore = torch.empty(nchunks, R, top_k, dtype=torch.float32, device=dev)
+    pidx = torch.empty(nchunks, R, top_k, dtype=torch.int32, device=dev)
+    idx = torch.zeros(B, Tmax, top_k, dtype=torch.int32, device=dev)
+    dist = torch.zeros(B, Tmax, top_k, dtype=torch.float32, device=dev)
+    bad = torch.zeros(B, dtype=torch.int32, device=dev)
+    xnorm = kmeans_row_norms(X.reshape(R, d))
+    call("mms2ut_kmeans_topk", X.data_ptr(), d, R, d, c_hi.data_ptr(), c_lo.data_ptr(), cnorm.data_ptr(), Kc, chunk,
+         top_k, pscore.data_ptr(), pidx.data_ptr(), _s())
+    call("mms2ut_kmeans_topk_fold", pscore.data_ptr(), pidx.data_ptr(), nchunks, B, Tmax, _p(lens), xnorm.data_ptr(),
+         top_k, idx.data_ptr(), dist.data_ptr(), bad.data_ptr(), _s())
+    return idx, dist, bad
+
+
+def units_beam(idx, dist, lens=None, *, beamsize=200):
+    """The reference's length-penalised beam search (mhubert.py HubertCode.decode, beamsearch=True, in
+    float32) over kmeans_topk's idx int32 / dist fp32 [B, Tmax, top_k] (or [T, top_k]), one block per
+    utterance of lens[b] frames; units.beam_decode_host is the host restatement it equals bit for bit.
+    -> (beam_code int32 [B, Tmax], beam_merged int32 [B, Tmax]: its runs collapsed, count int32 [B], bad int32
+    [B]: 1 where a frame's distances sum to 0 or to a non-finite value).  beamsize * top_k <= 2048."""
+    _chk(idx, torch.int32)
+    _chk(dist, torch.float32)
+    if idx.dim() == 2 and dist.dim() == 2:
+        idx, dist = idx.unsqueeze(0), dist.unsqueeze(0)
+    if idx.dim() != 3 or idx.shape != dist.shape or not idx.is_contiguous() or not dist.is_contiguous() \
+            or min(idx.shape) < 1 or dist.device != idx.device:
+        raise ValueError(f"units_beam: contiguous idx, dist [B, Tmax, top_k] expected, got {tuple(idx.shape)}, "
+                         f"{tuple(dist.shape)}")
+    B, Tmax, top_k = idx.shape
+    top_k, beamsize = check_beam_limits(top_k, beamsize)
+    if lens is not None:
+        _chk(lens, torch.int32)
+        assert lens.is_contiguous() and lens.numel() == B
+    dev = idx.device
+    nbytes = _lib.i64(0)
+    call("mms2ut_units_beam_ws", B, Tmax, beamsize, _lib.C.byref(nbytes))
+    ws = torch.empty(nbytes.value // 8, dtype=torch.int64, device=dev)
+    code = torch.zeros(B, Tmax, dtype=torch.int32, device=dev)
+    merged = torch.zeros(B, Tmax, dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    bad = torch.empty(B, dtype=torch.int32, device=dev)
+    call("mms2ut_units_beam", idx.data_ptr(), dist.data_ptr(), B, Tmax, _p(lens), top_k, beamsize, ws.data_ptr(),
+         code.data_ptr(), merged.data_ptr(), count.data_ptr(), bad.data_ptr(), _s())
+    return code, merged, count, bad
+
+
 # ============================================================================ unit codebook training (k-means)
 
 KMEANS_PP_MAX_TRIALS = _lib.KMEANS_PP_MAX_TRIALS

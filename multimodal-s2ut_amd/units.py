@@ -10,7 +10,12 @@ csrc/asr.hip's asr_conv; the post-LN layers run on the GEMM, LayerNorm and flash
 training path over utterances packed as [B, Tmax, d] with key-length masking; kmeans_assign quantises
 the packed rows without writing the [rows, centroids] distances.  Only ``km_layer`` layers are loaded
 and run.  The loaders, the layer loop and the packing are encoders.py's (SpeechEncoder, shared with
-asr.py); what is here is the group-norm feature extractor, the centroids and the units."""
+asr.py); what is here is the group-norm feature extractor, the centroids and the units.
+
+decode / decode_many are mhubert.py's HubertCode.decode at its defaults (beamsearch=True, top_k=10,
+beamsize=200): kmeans_topk keeps each frame's top_k nearest centroids and their Euclidean distances,
+units_beam (csrc/units_beam.hip) runs the reference's length-penalised beam search over them in its float32
+arithmetic, one block per utterance; beam_decode_host is the NumPy restatement the kernel equals bit for bit."""
 import os
 
 import numpy as np
@@ -78,6 +83,68 @@ def merge(code):
         if not out or out[-1] != c:
             out.append(c)
     return out
+
+
+def pairwise_sum(a):
+    """numpy.sum of up to 32 contiguous float32 values, in the order numpy adds them (its pairwise_sum below
+    the 128-element block), one float32 rounding per addition: sequential below 8 values; from 8 on, eight
+    accumulators over the whole groups of eight, ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)), then the tail one at a
+    time.  csrc/units_beam.hip adds in this order."""
+    a = np.asarray(a, dtype=np.float32)
+    k = a.shape[0]
+    if not 1 <= k <= K.KMEANS_TOPK_MAX:
+        raise NotImplementedError(f"pairwise_sum: 1 to {K.KMEANS_TOPK_MAX} values, got {k}")
+    if k < 8:
+        res = a[0]
+        for i in range(1, k):
+            res = np.float32(res + a[i])
+        return np.float32(res)
+    n8 = k - k % 8
+    r = a[:8].copy()
+    for i in range(8, n8, 8):
+        r = (r + a[i:i + 8]).astype(np.float32)
+    res = np.float32(np.float32(np.float32(r[0] + r[1]) + np.float32(r[2] + r[3]))
+                     + np.float32(np.float32(r[4] + r[5]) + np.float32(r[6] + r[7])))
+    for i in range(n8, k):
+        res = np.float32(res + a[i])
+    return res
+
+
+def beam_steps(idx, val, beamsize):
+    """The beam search of the reference's mhubert.py HubertCode.decode(beamsearch=True) as it evaluates
+    under NumPy >= 2 (all of it float32), frame by frame: yields (parent, token, score) arrays of the kept
+    sequences, in the reference's order.  A sequence is carried as (score, run count, last token); the
+    reference's stable sort over (sequence, j) order is a stable argsort of the flattened scores."""
+    idx, val = np.asarray(idx), np.asarray(val, dtype=np.float32)
+    if idx.ndim != 2 or idx.shape != val.shape or idx.shape[1] < 1:
+        raise ValueError(f"beam_decode_host: idx, val [T, top_k] expected, got {idx.shape}, {val.shape}")
+    T, k = idx.shape
+    K.check_beam_limits(k, beamsize)
+    score, runs, last = np.ones(1, dtype=np.float32), np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    for t in range(T):
+        s = pairwise_sum(val[t])
+        if not (np.isfinite(s) and s > 0):
+            raise NonFiniteFeatures(f"frame {t}: the {k} nearest distances sum to {s}")
+        r = (val[t] / s).astype(np.float32)
+        new = np.ones((len(score), k), dtype=bool) if t == 0 else idx[t][None, :] != last[:, None]
+        m = runs[:, None] + new
+        rate = (m.astype(np.float64) / np.float64(T)).astype(np.float32)
+        cand = (score[:, None] + (rate * r[None, :]).astype(np.float32)).astype(np.float32).reshape(-1)
+        keep = np.argsort(cand, kind="stable")[:beamsize]
+        parent, j = keep // k, keep % k
+        score, runs, last = cand[keep], m.reshape(-1)[keep], idx[t][j].astype(np.int64)
+        yield parent, last, score
+
+
+def beam_decode_host(idx, val, beamsize=200):
+    """beam_code of the reference's decode from the frames' top_k indices and distances [T, top_k] (host
+    restatement of kernels.units_beam, which equals it bit for bit) -> a list of T units."""
+    steps = [(p, tok) for p, tok, _ in beam_steps(idx, val, beamsize)]
+    out, p = [], 0
+    for parent, tok in reversed(steps):
+        out.append(int(tok[p]))
+        p = int(parent[p])
+    return out[::-1]
 
 
 class HubertUnits(SpeechEncoder):
@@ -168,6 +235,51 @@ class HubertUnits(SpeechEncoder):
             res += [(code[b, :lens[b]].tolist(), merged[b, :count[b]].tolist()) for b in range(len(lens))]
         return res
 
+    def decode(self, wave, beamsearch=True, top_k=10, beamsize=200, sr=None):
+        """The reference's mhubert.py HubertCode.decode of one utterance (decode_many's dict)."""
+        return self.decode_many([wave], 1, beamsearch, top_k, beamsize, sr)[0]
+
+    def decode_many(self, waves, batch_size=8, beamsearch=True, top_k=10, beamsize=200, sr=None):
+        """The reference's HubertCode.decode of every waveform, in order -> a list of dicts: ``code`` [T] and
+        ``merged_code`` (lists), ``topk_code`` int32 [T, top_k] and ``topk_distance`` fp32 [T, top_k] (numpy: the
+        top_k nearest centroids of each frame and their Euclidean distances, ascending; ties to the lower
+        index) and, with beamsearch, ``beam_code`` [T] and ``beam_merged_code`` (lists): the length-penalised
+        beam search over them, kernels.kmeans_topk and kernels.units_beam.  The reference's ``distance``
+        ([T, centroids], the matrix kmeans_topk exists not to write) and ``center_diff`` are not returned.
+        One host read per batch of batch_size utterances."""
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        if self.c_hi is None:
+            raise RuntimeError("this HubertUnits was loaded without centroids: it extracts features only")
+        top_k, beamsize = K.check_beam_limits(top_k, beamsize if beamsearch else 1)
+        waves, res = list(waves), []
+        for i in range(0, len(waves), batch_size):
+            Fb, lens, lens32 = self.features_batch(waves[i:i + batch_size], sr)
+            B, Tm = Fb.shape[:2]
+            idx, dist, bad = K.kmeans_topk(Fb, self.c_hi, self.c_lo, self.c_norm, lens32, top_k=top_k)
+            parts = [idx.reshape(B, -1), dist.view(torch.int32).reshape(B, -1), bad[:, None]]
+            if beamsearch:
+                beam, bmerged, bcount, bbad = K.units_beam(idx, dist, lens32, beamsize=beamsize)
+                parts += [beam, bmerged, bcount[:, None], bbad[:, None]]
+            host = torch.cat(parts, 1).cpu().numpy()            # the batch's one host read
+            n = Tm * top_k
+            for b, T in enumerate(lens):
+                row = host[b]
+                if row[2 * n] or (beamsearch and row[-1]):
+                    raise NonFiniteFeatures(f"utterance {i + b} ({T} frames): non-finite features (the fp16 "
+                                            "activations overflowed) or a frame at zero distance from its "
+                                            f"{top_k} nearest centroids; no units written")
+                tk = row[:n].reshape(Tm, top_k)[:T].copy()
+                code = tk[:, 0].tolist()
+                out = {"code": code, "merged_code": merge(code), "topk_code": tk,
+                       "topk_distance": row[n:2 * n].view(np.float32).reshape(Tm, top_k)[:T].copy()}
+                if beamsearch:
+                    o = 2 * n + 1
+                    out["beam_code"] = row[o:o + T].tolist()
+                    out["beam_merged_code"] = row[o + Tm:o + Tm + int(row[o + 2 * Tm])].tolist()
+                res.append(out)
+        return res
+
 
 def read_manifest(path):
     """fairseq's manifest: the root directory on the first line, then ``relative/path<TAB>n_samples``.
@@ -187,13 +299,21 @@ def read_manifest(path):
     return lines[0].strip(), files
 
 
-def quantize_manifest(model, manifest_path, out_path, extension=".wav", batch_size=8, reduce=False):
+def quantize_manifest(model, manifest_path, out_path, extension=".wav", batch_size=8, reduce=False, beamsearch=False,
+                      top_k=10, beamsize=200):
     """Units of every file of the manifest, in its order, one line each:
-    ``{basename without extension}|{units joined by spaces}``.  -> the number of files."""
+    ``{basename without extension}|{units joined by spaces}``.  beamsearch: the beam decode's units
+    (decode_many's beam_code, or beam_merged_code with reduce) instead of the nearest centroids.
+    -> the number of files."""
     root, files = read_manifest(manifest_path)
     lines = []
     for names, waves in wave_batches(root, files, batch_size, model.sampling_rate, model.min_samples):
-        for f, (code, merged) in zip(names, model.units_many(waves, batch_size)):
+        if beamsearch:
+            pairs = [(r["beam_code"], r["beam_merged_code"])
+                     for r in model.decode_many(waves, batch_size, True, top_k, beamsize)]
+        else:
+            pairs = model.units_many(waves, batch_size)
+        for f, (code, merged) in zip(names, pairs):
             base = os.path.basename(f)
             if extension and base.endswith(extension):
                 base = base[:-len(extension)]

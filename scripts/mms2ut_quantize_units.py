@@ -10,7 +10,9 @@ optionally preprocessor_config.json); fairseq's .pt checkpoints are not read.  -
 joblib-pickled scikit-learn k-means or a .npy file of its cluster_centers_.  The manifest is fairseq's: the
 root directory on the first line, then ``relative/path<TAB>n_samples``.  One line per file comes out, in
 manifest order: ``{basename without extension}|{units joined by spaces}``; --reduce collapses runs of
-equal units."""
+equal units.  --beamsearch [--top_k 10] [--beamsize 200] writes the units of the reference's own decode
+(scripts/speech_to_speech_translation/mhubert.py, beamsearch=True) instead: a length-penalised beam search
+over each frame's top_k nearest centroids."""
 import argparse
 import importlib
 import os
@@ -31,6 +33,11 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=8, help="utterances per encoder batch")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--reduce", action="store_true", help="write the units with runs collapsed")
+    ap.add_argument("--beamsearch", action="store_true",
+                    help="write the reference's beam decode (mhubert.py HubertCode.decode) instead of the nearest centroids")
+    ap.add_argument("--top_k", type=int, default=10, help="with --beamsearch: nearest centroids per frame (at most 32)")
+    ap.add_argument("--beamsize", type=int, default=200,
+                    help="with --beamsearch: sequences kept per frame (beamsize x top_k at most 2048)")
     args = ap.parse_args(argv)
     if args.feature_type != "hubert":
         ap.error(f"--feature_type '{args.feature_type}' is not supported (only 'hubert')")
@@ -42,7 +49,7 @@ def main(argv=None):
     U = importlib.import_module("multimodal-s2ut_amd.units")
     model = U.HubertUnits.from_pretrained(args.acoustic_model_path, args.kmeans_model_path, args.layer, args.device)
     n = U.quantize_manifest(model, args.manifest_path, args.out_quantized_file_path, args.extension, args.batch_size,
-                            args.reduce)
+                            args.reduce, args.beamsearch, args.top_k, args.beamsize)
     print(f"quantised {n} files to {args.out_quantized_file_path}", file=sys.stderr)
     return 0
 
