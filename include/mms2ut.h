@@ -429,6 +429,23 @@ int mms2ut_ls_xent_eval(const mms2ut_half* logits, int64_t ld, const int64_t* ta
 int mms2ut_ls_xent_bwd(const mms2ut_half* logits, int64_t ld, const int64_t* target, int64_t rows,
                        int V, float eps, int pad_idx, const float* lse, const float* grad,
                        mms2ut_half* dlogits, hipStream_t stream);
+/* R-Drop (fairseq RdropLabelSmoothedCrossEntropyCriterion, --rdrop-alpha; the reference's
+ * criterions/speech_to_speech_criterion.py:46-56, :70-76): logits [rows = 2R, ld] hold two dropout
+ * passes over the same R targets (row r and row r + R), target[R] are the first half's.  One wave
+ * per pair.  kl = 1/2 sum over non-pad pairs of sum_v (p_v - q_v)(log p_v - log q_v)
+ * (compute_kl_loss), loss = the label-smoothed CE over all 2R rows + alpha * kl.  lse[rows] as
+ * mms2ut_ls_xent_fwd writes it for non-pad rows (bit-identical), 0 for pad pairs (their logits are
+ * not read).  Block partials of {loss, nll, kl} in part[3 * MMS_LS_XENT_PARTS], summed in a fixed
+ * order: acc[0..1] += {loss, nll}, acc_kl[0] += kl, call_out[0..2] = {loss, nll, kl} (each may be
+ * NULL, not all).  rows even, ld % 4 == 0, ld >= V, 2 <= V <= 4096, logits 8-byte aligned.      */
+int mms2ut_ls_xent_rdrop_fwd(const mms2ut_half* logits, int64_t ld, const int64_t* target, int64_t rows,
+                             int V, float eps, int pad_idx, float alpha, float* lse, float* part,
+                             float* acc, float* acc_kl, float* call_out, hipStream_t stream);
+/* dlogits = grad * [(p - y_smooth) + alpha * dkl/dz] for both rows of every pair, 0 on pad pairs
+ * and on the pad columns [V, ld); in place OK.  The KL sums are recomputed from lse.            */
+int mms2ut_ls_xent_rdrop_bwd(const mms2ut_half* logits, int64_t ld, const int64_t* target, int64_t rows,
+                             int V, float eps, int pad_idx, float alpha, const float* lse,
+                             const float* grad, mms2ut_half* dlogits, hipStream_t stream);
 
 /* ---------------------------------------------------------------- FP16Optimizer + Adam
  * fairseq FP16Optimizer (fp32 master, dynamic loss scale) + clip_grad_norm_ + Adam (fairseq

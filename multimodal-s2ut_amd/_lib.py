@@ -289,6 +289,8 @@ SIGNATURES = {
     "mms2ut_ls_xent_fwd_log": (i32, [vp, i64, vp, i64, i32, f32, i32, vp, vp, vp, vp, vp]),
     "mms2ut_ls_xent_eval": (i32, [vp, i64, vp, i64, i32, f32, i32, vp, vp, vp]),
     "mms2ut_ls_xent_bwd": (i32, [vp, i64, vp, i64, i32, f32, i32, vp, vp, vp, vp]),
+    "mms2ut_ls_xent_rdrop_fwd": (i32, [vp, i64, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, vp, vp]),
+    "mms2ut_ls_xent_rdrop_bwd": (i32, [vp, i64, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp]),
     "mms2ut_grad_sqnorm": (i32, [vp, i64, vp, i32, vp]),
     "mms2ut_grad_norm_finalize": (i32, [vp, i32, vp, vp, vp]),
     "mms2ut_stream_wait": (i32, [vp, vp]),

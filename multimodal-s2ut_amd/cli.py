@@ -290,13 +290,21 @@ def _log(args, upd, log, tr, ntok, t0, rank):
     st = tr.opt.check_fatal()
     if rank != 0:
         return
-    lg = log.tolist()
-    el = time.time() - t0
+    print(json.dumps(log_record(upd, log.tolist(), st, ntok, time.time() - t0)), flush=True)
+
+
+def log_record(upd, lg, st, ntok, el):
+    """One train log record from the step log ``lg`` (trainer.LOG_* slots; sample size = ntokens):
+    loss / nll_loss in base 2 per target token.  A sixth slot (R-Drop, --rdrop-alpha > 0) adds
+    rdrop_kl_loss = kl sum / sample_size / ln 2 as fairseq logs it; loss and nll_loss are then sums
+    over both dropout passes, roughly double the plain values."""
     ln2 = math.log(2)
     rec = {"num_updates": upd, "loss": lg[0] / lg[2] / ln2, "nll_loss": lg[1] / lg[2] / ln2,
            "ppl": 2 ** (lg[1] / lg[2] / ln2), "wps": ntok / max(el, 1e-9), "ups": upd / max(el, 1e-9),
            "lr": st["lr"], "gnorm": st["gnorm"], "loss_scale": st["loss_scale"], "overflow": st["overflow"]}
-    print(json.dumps(rec), flush=True)
+    if len(lg) > 5:
+        rec["rdrop_kl_loss"] = lg[5] / lg[2] / ln2
+    return rec
 
 
 if __name__ == "__main__":

@@ -191,6 +191,215 @@ __global__ void __launch_bounds__(256) ls_xent_bwd_kernel(const h16* __restrict_
   for (long j = V + lane; j < ld; j += 64) dz[row * ld + j] = (h16)0.f;
 }
 
+// ---------------------------------------------------------------------------------- R-Drop
+// fairseq RdropLabelSmoothedCrossEntropyCriterion (--rdrop-alpha): logits [2R, ld] are two dropout
+// passes over the same R target rows (row r and row r + R), target[R] are the first half's.  One
+// wave per pair: both rows stay in registers as the fp16 they were loaded as, so the forward reads
+// the logits once and the backward reads and writes them once.
+//   kl   = 1/2 sum_{r: target_r != pad} sum_v (p_v - q_v)(lp_v - lq_v)   (compute_kl_loss)
+//   loss = CE over all 2R rows + alpha * kl
+
+// One row's {max, sum of logits, lse} with ls_xent_fwd_kernel's arithmetic (same loads, same order
+// of operations: the lse is bit-identical to that kernel's); t[c] keeps the row's fp16 chunks.
+template <int CPL>
+MMS_DEV void rdrop_row_stats(const h16* __restrict__ zr, int V, int lane, h16x4 (&t)[CPL], float& sum_out,
+                             float& lse_out) {
+  float mx = -INFINITY, sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) {
+    const int j0 = (lane + c * 64) * 4;
+    t[c] = h16x4{(h16)0.f, (h16)0.f, (h16)0.f, (h16)0.f};
+    if (j0 < V) {
+      t[c] = *reinterpret_cast<const h16x4*>(zr + j0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (j0 + e < V) { const float x = (float)t[c][e]; mx = fmaxf(mx, x); sum += x; }
+    }
+  }
+  mx = wave_max(mx);
+  sum = wave_sum(sum);
+  float se = 0.f;
+#pragma unroll
+  for (int c = 0; c < CPL; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) se += ((lane + c * 64) * 4 + e < V) ? __expf((float)t[c][e] - mx) : 0.f;
+  se = wave_sum(se);
+  sum_out = sum;
+  lse_out = mx + __logf(se);
+}
+
+template <int CPL>
+__global__ void __launch_bounds__(256) ls_xent_rdrop_fwd_kernel(const h16* __restrict__ z, long ld,
+                                                                const int64_t* __restrict__ target, long R,
+                                                                int V, float eps, int pad, float alpha,
+                                                                float* __restrict__ lse_out,
+                                                                float* __restrict__ part) {
+  __shared__ float red[3][4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float loss = 0.f, nll = 0.f, kl = 0.f;
+  // grid-stride over pairs on a bounded grid, as ls_xent_fwd_kernel over rows; each block leaves
+  // its {loss, nll, kl} partial (loss = CE + alpha * kl), summed in block order afterwards
+  for (long r = (long)blockIdx.x * 4 + w; r < R; r += (long)gridDim.x * 4) {
+    const int64_t t = target[r];   // wave-uniform: a pad pair costs no logits traffic
+    if (t == pad) {
+      if (lane == 0) { lse_out[r] = 0.f; lse_out[r + R] = 0.f; }   // never read: a defined value
+      continue;
+    }
+    const h16* zp = z + r * ld;
+    const h16* zq = z + (r + R) * ld;
+    h16x4 tp[CPL], tq[CPL];
+    float sum_p, sum_q, lse_p, lse_q;
+    rdrop_row_stats<CPL>(zp, V, lane, tp, sum_p, lse_p);
+    rdrop_row_stats<CPL>(zq, V, lane, tq, sum_q, lse_q);
+    if (lane == 0) { lse_out[r] = lse_p; lse_out[r + R] = lse_q; }
+    // d = lp - lq from the logits (their fp16 difference is exact in fp32) and the two lse, never
+    // from log(p): identical halves give d == 0 and p == q exactly, so kl == 0.0
+    const float dl = lse_p - lse_q;
+    float k = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((lane + c * 64) * 4 + e < V) {
+          const float a = (float)tp[c][e], b = (float)tq[c][e];
+          const float d = (a - b) - dl;
+          k += (__expf(a - lse_p) - __expf(b - lse_q)) * d;
+        }
+    k = wave_sum(k);
+    // a target outside [0, V) poisons the sums instead of reading past the row
+    const bool ok = t >= 0 && t < V;
+    const float ztp = ok ? (float)zp[t] : NAN, ztq = ok ? (float)zq[t] : NAN;
+    const float eps_i = eps / (V - 1);
+    const float nlp = lse_p - ztp, nlq = lse_q - ztq;
+    nll += nlp;
+    loss += (1.f - eps - eps_i) * nlp + eps_i * (V * lse_p - sum_p);
+    nll += nlq;
+    loss += (1.f - eps - eps_i) * nlq + eps_i * (V * lse_q - sum_q);
+    kl += 0.5f * k;
+  }
+  if (lane == 0) { red[0][w] = loss + alpha * kl; red[1][w] = nll; red[2][w] = kl; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int k = threadIdx.x;
+    part[(long)k * gridDim.x + blockIdx.x] = red[k][0] + red[k][1] + red[k][2] + red[k][3];
+  }
+}
+
+// the nb block partials of {loss, nll, kl} summed in a fixed order, one wave per value:
+// acc[0..1] += {loss, nll}, acc_kl[0] += kl, call_out[0..2] = {loss, nll, kl} (each may be null)
+__global__ void __launch_bounds__(192) ls_xent_rdrop_sum_kernel(const float* __restrict__ part, int nb,
+                                                                float* __restrict__ acc, float* __restrict__ acc_kl,
+                                                                float* __restrict__ call_out) {
+  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+  float s = 0.f;
+  for (int i = lane; i < nb; i += 64) s += part[(long)k * nb + i];
+  s = wave_sum(s);
+  if (lane == 0) {
+    if (k < 2 && acc) acc[k] += s;
+    if (k == 2 && acc_kl) acc_kl[0] += s;
+    if (call_out) call_out[k] = s;
+  }
+}
+
+// fp16(a * x + m), two ways.  ls_xent_bwd_kernel's `(h16)(a * x + m)` compiles to one of them per
+// element: elements 0 and 3 of a lane's 4-column chunk become v_fma_mixlo_f16, which rounds the
+// exact a * x + m to fp16 once; elements 1 and 2 are paired into v_pk_fma_f32 + v_cvt_pk_f16_f32,
+// which round to fp32 and then to fp16.  The two differ by one fp16 ulp in about 1 element of
+// 40,000 (measured).  The R-Drop backward spells the same choice out, so its CE half is that
+// kernel's bit for bit (tests/test_gpu_rdrop.py pins it; if a compiler ever pairs ls_xent_bwd's
+// elements differently that test says so and this choice moves with it).
+MMS_DEV h16 fma_h16_fused(float a, float x, float m) {
+  unsigned r = 0;
+  asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "+v"(r) : "v"(a), "v"(x), "v"(m));
+  return __builtin_bit_cast(h16, (unsigned short)r);
+}
+MMS_DEV h16 fma_h16_unfused(float a, float x, float m) {
+  float f = __builtin_fmaf(a, x, m);
+  asm volatile("" : "+v"(f));   // keeps the fp32 rounding: no folding into a mixed-precision fma
+  return (h16)f;
+}
+
+// In place over the logits: dz = grad * [(p - y_smooth) + alpha * dkl/dz] for both rows of a pair,
+// zeros for pad pairs and the pad columns [V, ld).  With d = lp - lq, K1 = sum p d, K2 = -sum q d:
+//   dkl/dz^p_j = 1/2 [p_j (d_j - K1) + p_j - q_j],  dkl/dz^q_j = 1/2 [q_j (-d_j - K2) + q_j - p_j]
+// K1 / K2 are recomputed from the saved lse (one more pass over the registers, nothing saved per
+// pair).  The CE part is ls_xent_bwd_kernel's expression and rounding (fma_h16_* above); the KL
+// part is exactly 0 for identical halves, so the gradient is then that kernel's bit for bit.
+template <int CPL>
+__global__ void __launch_bounds__(256) ls_xent_rdrop_bwd_kernel(const h16* __restrict__ z, long ld,
+                                                                const int64_t* __restrict__ target, long R,
+                                                                int V, float eps, int pad, float alpha,
+                                                                const float* __restrict__ lse,
+                                                                const float* __restrict__ grad, h16* __restrict__ dz) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int64_t t = target[r];
+  h16* dp = dz + r * ld;
+  h16* dq = dz + (r + R) * ld;
+  if (t == pad) {   // wave-uniform: zeros without reading the logits
+    const h16x4 zero{(h16)0.f, (h16)0.f, (h16)0.f, (h16)0.f};
+    for (long j = (long)lane * 4; j < ld; j += 256) {
+      *reinterpret_cast<h16x4*>(dp + j) = zero;
+      *reinterpret_cast<h16x4*>(dq + j) = zero;
+    }
+    return;
+  }
+  const float g = grad[0];
+  const float eps_i = eps / (V - 1);
+  const float a = g * (1.f - eps - eps_i);
+  const float bsm = g * eps_i;
+  const float gk = g * alpha * 0.5f;
+  const float Lp = lse[r], Lq = lse[r + R];
+  const float dl = Lp - Lq;
+  h16x4 tp[CPL], tq[CPL];
+  float K1 = 0.f, K2 = 0.f;
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) {
+    const int j0 = (lane + c * 64) * 4;
+    if (j0 < V) {
+      tp[c] = *reinterpret_cast<const h16x4*>(z + r * ld + j0);
+      tq[c] = *reinterpret_cast<const h16x4*>(z + (r + R) * ld + j0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (j0 + e < V) {
+          const float x = (float)tp[c][e], y = (float)tq[c][e];
+          const float d = (x - y) - dl;
+          K1 += __expf(x - Lp) * d;
+          K2 -= __expf(y - Lq) * d;
+        }
+    }
+  }
+  K1 = wave_sum(K1);
+  K2 = wave_sum(K2);
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) {
+    const int j0 = (lane + c * 64) * 4;
+    if (j0 < V) {
+      h16x4 op, oq;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int j = j0 + e;
+        const float x = (float)tp[c][e], y = (float)tq[c][e];
+        const float p = __expf(x - Lp), q = __expf(y - Lq);
+        const float d = (x - y) - dl;
+        const float oh = (j == t) ? 1.f : 0.f;
+        // a (p - onehot) + [bsm (V p - 1) + the KL part]: the KL part is exactly 0 for identical
+        // halves, which leaves ls_xent_bwd_kernel's fma(a, p - onehot, bsm (V p - 1))
+        const float mp = bsm * __builtin_fmaf(p, (float)V, -1.f) + gk * (p * (d - K1) + (p - q));
+        const float mq = bsm * __builtin_fmaf(q, (float)V, -1.f) + gk * (q * (-d - K2) + (q - p));
+        const h16 hp = (e == 0 || e == 3) ? fma_h16_fused(a, p - oh, mp) : fma_h16_unfused(a, p - oh, mp);
+        const h16 hq = (e == 0 || e == 3) ? fma_h16_fused(a, q - oh, mq) : fma_h16_unfused(a, q - oh, mq);
+        op[e] = (j < V) ? hp : (h16)0.f;
+        oq[e] = (j < V) ? hq : (h16)0.f;
+      }
+      *reinterpret_cast<h16x4*>(dp + j0) = op;
+      *reinterpret_cast<h16x4*>(dq + j0) = oq;
+    }
+  }
+  for (long j = V + lane; j < ld; j += 64) { dp[j] = (h16)0.f; dq[j] = (h16)0.f; }
+}
+
 __global__ void grad_sqnorm_kernel(const h16* __restrict__ g, long n, float* __restrict__ part) {
   __shared__ float red[4];
   float s = 0.f;
@@ -462,6 +671,53 @@ extern "C" int mms2ut_ls_xent_bwd(const h16* logits, int64_t ld, const int64_t* 
     hipLaunchKernelGGL((ls_xent_bwd_kernel<decltype(C)::value>), dim3((rows + 3) / 4), dim3(256), 0, s,
                        logits, (long)ld, target, (long)rows, V, eps, pad_idx, lse, grad, dlogits);
     return mms::check_launch("ls_xent_bwd");
+  });
+}
+
+static int rdrop_check(const char* who, const h16* logits, int64_t ld, int64_t rows, int V) {
+  MMS_REQUIRE(rows >= 0 && rows % 2 == 0, "%s: rows must be even (two passes over the same targets), got %ld", who,
+              (long)rows);
+  MMS_REQUIRE(ld % 4 == 0 && ld >= V, "%s: ld must be a multiple of 4 and >= V", who);
+  MMS_REQUIRE(((uintptr_t)logits & 7) == 0, "%s: logits must be 8-byte aligned", who);
+  MMS_REQUIRE(V >= 2 && V <= 64 * 4 * 16, "%s: vocabulary size out of range (%d)", who, V);
+  return 0;
+}
+
+extern "C" int mms2ut_ls_xent_rdrop_fwd(const h16* logits, int64_t ld, const int64_t* target, int64_t rows, int V,
+                                        float eps, int pad_idx, float alpha, float* lse, float* part, float* acc,
+                                        float* acc_kl, float* call_out, hipStream_t s) {
+  if (rdrop_check("ls_xent_rdrop_fwd", logits, ld, rows, V)) return 1;
+  MMS_REQUIRE(part && lse && (acc || acc_kl || call_out), "ls_xent_rdrop_fwd: null partials / lse / loss");
+  if (rows == 0) {
+    if (call_out) {
+      const float z[3] = {0.f, 0.f, 0.f};
+      return mms2ut_set_f32(call_out, 3, z, s);
+    }
+    return 0;
+  }
+  const long R = rows / 2;
+  const int nb = (int)std::min<long>((R + 3) / 4, MMS_LS_XENT_PARTS);
+  const int rc = pick_cpl_v(V, [&](auto C) {
+    hipLaunchKernelGGL((ls_xent_rdrop_fwd_kernel<decltype(C)::value>), dim3(nb), dim3(256), 0, s,
+                       logits, (long)ld, target, R, V, eps, pad_idx, alpha, lse, part);
+    return mms::check_launch("ls_xent_rdrop_fwd");
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(ls_xent_rdrop_sum_kernel, dim3(1), dim3(192), 0, s, part, nb, acc, acc_kl, call_out);
+  return mms::check_launch("ls_xent_rdrop_sum");
+}
+
+extern "C" int mms2ut_ls_xent_rdrop_bwd(const h16* logits, int64_t ld, const int64_t* target, int64_t rows, int V,
+                                        float eps, int pad_idx, float alpha, const float* lse, const float* grad,
+                                        h16* dlogits, hipStream_t s) {
+  if (rdrop_check("ls_xent_rdrop_bwd", logits, ld, rows, V)) return 1;
+  MMS_REQUIRE(((uintptr_t)dlogits & 7) == 0, "ls_xent_rdrop_bwd: dlogits must be 8-byte aligned");
+  if (rows == 0) return 0;
+  const long R = rows / 2;
+  return pick_cpl_v(V, [&](auto C) {
+    hipLaunchKernelGGL((ls_xent_rdrop_bwd_kernel<decltype(C)::value>), dim3((R + 3) / 4), dim3(256), 0, s,
+                       logits, (long)ld, target, R, V, eps, pad_idx, alpha, lse, grad, dlogits);
+    return mms::check_launch("ls_xent_rdrop_bwd");
   });
 }
 

@@ -1209,6 +1209,28 @@ def ls_xent_bwd(logits, ld, target, rows, V, eps, pad, lse, grad, out):
     return out
 
 
+def ls_xent_rdrop_fwd(logits, ld, target, rows, V, eps, pad, alpha, acc=None, acc_kl=None, call_out=None):
+    """R-Drop forward over logits [rows = 2R, ld] (two dropout passes, row r pairs with row r + R)
+    and the first half's targets [R]: acc[0:2] += {CE over 2R rows + alpha * kl, nll},
+    acc_kl[0] += kl, call_out[0:3] = this call's {loss, nll, kl} (fixed-order sums; each may be
+    None, not all); returns lse [rows] (0 on pad pairs)."""
+    _chk(logits)
+    _chk(target, torch.int64)
+    assert target.numel() >= rows // 2 and logits.numel() >= rows * ld
+    lse = torch.empty(max(rows, 1), dtype=torch.float32, device=logits.device)[:rows]
+    part = _workspace("ls_xent_rdrop_part", 3 * LS_XENT_PARTS, logits.device)
+    call("mms2ut_ls_xent_rdrop_fwd", logits.data_ptr(), ld, target.data_ptr(), rows, V, float(eps), pad,
+         float(alpha), lse.data_ptr(), part.data_ptr(), _p(acc), _p(acc_kl), _p(call_out), _s())
+    return lse
+
+
+def ls_xent_rdrop_bwd(logits, ld, target, rows, V, eps, pad, alpha, lse, grad, out):
+    """out (may be ``logits``) = grad * [(p - y_smooth) + alpha * dkl/dz] for both halves."""
+    call("mms2ut_ls_xent_rdrop_bwd", logits.data_ptr(), ld, target.data_ptr(), rows, V, float(eps), pad,
+         float(alpha), lse.data_ptr(), grad.data_ptr(), out.data_ptr(), _s())
+    return out
+
+
 OST_MULT, OST_GNORM, OST_OVERFLOW, OST_STEP, OST_STEP_SIZE, OST_LOSS_SCALE, OST_ITER, \
     OST_LAST_OVERFLOW, OST_LAST_RESCALE, OST_CLIP_COEF, OST_FATAL, OST_LR, OST_INCONSISTENT = range(13)
 OST_SIZE = 16

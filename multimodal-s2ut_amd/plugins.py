@@ -105,6 +105,14 @@ def mm_s2ut_architecture_base(args):
     s2ut_architecture_base(args)
 
 
+def check_rdrop_alpha(alpha):
+    """--rdrop-alpha (fairseq RdropLabelSmoothedCrossEntropyCriterion): a float >= 0, None = 0."""
+    alpha = 0.0 if alpha is None else float(alpha)
+    if not alpha >= 0.0:
+        raise ValueError(f"--rdrop-alpha must be >= 0 (got {alpha})")
+    return alpha
+
+
 def cfg_from_args(args, fusion_cfg=None, vocab_size=1004):
     """fairseq args Namespace (+ fusion YAML) -> model config dict."""
     mm_s2ut_architecture_base(args)
@@ -133,6 +141,9 @@ def cfg_from_args(args, fusion_cfg=None, vocab_size=1004):
         vocab_size=vocab_size, max_source_positions=args.max_source_positions,
         max_target_positions=args.max_target_positions, no_scale_embedding=args.no_scale_embedding,
         label_smoothing=getattr(args, "label_smoothing", 0.2), fusion=False)
+    alpha = check_rdrop_alpha(getattr(args, "rdrop_alpha", 0.0))
+    if alpha > 0:      # the native trainer's switch (trainer.Trainer); absent = the plain step
+        cfg["rdrop_alpha"] = alpha
     if fusion_cfg is not None:
         dims = fusion_cfg.image_feat_dim
         dims = list(dims) if isinstance(dims, (list, tuple)) else [dims]
@@ -244,7 +255,8 @@ class MultiModalSpeechToSpeechTask:
         return out
 
     def build_criterion(self, args):
-        return SpeechToUnitCriterion(self, getattr(args, "label_smoothing", 0.2))
+        return SpeechToUnitCriterion(self, getattr(args, "label_smoothing", 0.2),
+                                     rdrop_alpha=getattr(args, "rdrop_alpha", 0.0))
 
     def load_dataset(self, split, epoch=1, **kw):
         """speech_to_speech.py:100-123 -> the on-disk manifest (manifest.MultiModalS2SManifest)."""
@@ -524,8 +536,10 @@ class MM_S2UTTransformerModel:
 
     def forward(self, src_tokens, src_lengths, prev_output_tokens, src_audio_path=None, img_path=None,
                 img_tensor=None, imgs_list=(), img_masks_list=(), tgt_speaker=None,
-                return_all_hiddens=False, target=None, multitask=None, **kwargs):
+                return_all_hiddens=False, target=None, multitask=None, duplicate_input=False, **kwargs):
         """Reference signature (mm_s2s_transformer.py:667-680) -> (logits [B, Tt, V], extra).
+        duplicate_input (R-Drop): the prepared batch is concatenated with itself
+        (runtime.duplicate_batch), so the outputs and extra["_batch"] hold 2B sentences.
         The logits are autograd-connected to the hand-written backward.  return_all_hiddens adds
         ``encoder_states`` (L_e layer outputs, [Te, B, C]) and ``encoder_padding_mask`` to extra
         as the reference does (:697-699)."""
@@ -533,6 +547,8 @@ class MM_S2UTTransformerModel:
             raise NotImplementedError("target speaker embeddings (spk_emb_proj) are out of scope")
         batch = self._batch(src_tokens, src_lengths, prev_output_tokens, imgs_list, img_masks_list, target,
                             multitask, extra_input=kwargs)
+        if duplicate_input:
+            batch = runtime.duplicate_batch(batch)
         stash = {}
         if return_all_hiddens:
             self.net.encoder_hook = stash.__setitem__
@@ -540,7 +556,7 @@ class MM_S2UTTransformerModel:
             logits, aux = runtime.model_outputs(self.net, batch)
         finally:
             self.net.encoder_hook = None
-        B, Tt = prev_output_tokens.shape
+        B, Tt = batch.prev.shape
         V = self.cfg["vocab_size"]
         out = logits.view(B, Tt, -1)[:, :, :V]
         extra = {"attn": [None], "inner_states": None, "_batch": batch, "_logits_padded": logits, "_aux_loss": aux}
@@ -558,25 +574,45 @@ class MM_S2UTTransformerModel:
 @register_criterion("speech_to_unit", "speech_to_speech", "speech_to_unit_v2")
 class SpeechToUnitCriterion:
     """fairseq speech_to_unit (ref copy criterions/speech_to_speech_criterion.py:58-102):
-    label-smoothed NLL (eps), reduce=sum, sample_size = ntokens (sentence_avg False)."""
+    label-smoothed NLL (eps), reduce=sum, sample_size = ntokens (sentence_avg False).  With
+    rdrop_alpha > 0 (fairseq --rdrop-alpha; :46-56, :70-76) a training forward runs the batch
+    duplicated and adds alpha * the symmetric KL of the two dropout passes: loss / nll_loss are
+    then sums over both passes, rdrop_kl_loss joins the logging output, and sample_size, ntokens
+    and nsentences stay those of the un-duplicated batch."""
 
-    def __init__(self, task, label_smoothing=0.2, sentence_avg=False):
+    def __init__(self, task, label_smoothing=0.2, sentence_avg=False, rdrop_alpha=0.0):
         self.eps = label_smoothing
         self.sentence_avg = sentence_avg
         self.padding_idx = getattr(task, "padding_idx", 1)
+        self.rdrop_alpha = check_rdrop_alpha(rdrop_alpha)
 
     def __call__(self, model, sample, reduce=True):
         return self.forward(model, sample, reduce)
 
     def forward(self, model, sample, reduce=True):
         ni = dict(sample["net_input"])
-        _, extra = model(**ni, target=sample["target"], multitask=sample.get("multitask"))
-        batch, logits = extra["_batch"], extra["_logits_padded"]
-        loss, nll = runtime.label_smoothed_ce(logits, batch.target, model.cfg["vocab_size"], self.eps,
-                                              self.padding_idx)
+        # validation stays un-duplicated (as Trainer.validate): fairseq would log twice the CE and a KL
+        # of ~0 in eval mode, which orders checkpoints the same
+        A = self.rdrop_alpha if model.net.training else 0.0
+        runtime.warn_rdrop_multitask(model.cfg, A)
+        if A > 0:
+            # fairseq duplicate_input: one forward over the batch concatenated with itself; the
+            # criterion pairs row r with row r + R and takes the un-duplicated targets
+            _, extra = model(**ni, target=sample["target"], multitask=sample.get("multitask"), duplicate_input=True)
+            batch, logits = extra["_batch"], extra["_logits_padded"]
+            R = batch.target.shape[0] // 2
+            loss, nll, kl = runtime.label_smoothed_ce_rdrop(logits, batch.target[:R], model.cfg["vocab_size"],
+                                                            self.eps, self.padding_idx, A)
+        else:
+            _, extra = model(**ni, target=sample["target"], multitask=sample.get("multitask"))
+            batch, logits = extra["_batch"], extra["_logits_padded"]
+            loss, nll = runtime.label_smoothed_ce(logits, batch.target, model.cfg["vocab_size"], self.eps,
+                                                  self.padding_idx)
         sample_size = sample["target"].size(0) if self.sentence_avg else sample["ntokens"]
         logging_output = {"loss": loss.detach(), "nll_loss": nll.detach(), "ntokens": sample["ntokens"],
                           "nsentences": sample["target"].size(0), "sample_size": sample_size}
+        if A > 0:
+            logging_output["rdrop_kl_loss"] = kl.detach()
         if model.cfg.get("multitask"):
             # fairseq SpeechToUnitMultitaskTaskCriterion: loss += sum_t weight_t * loss_t; the logged
             # "loss" is the main one, the heads are logged under "multitask"
@@ -603,6 +639,13 @@ class _TrainParser(argparse.ArgumentParser):
         return ns, rest
 
 
+def _rdrop_alpha_arg(text):
+    try:
+        return check_rdrop_alpha(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def build_parser():
     """Flag subset of the canonical command (scripts/textless/1_train.sh:105-125)."""
     p = _TrainParser("mms2ut-train")
@@ -611,6 +654,10 @@ def build_parser():
     p.add_argument("--arch", default="mm_s2ut_transformer")
     p.add_argument("--criterion", default="speech_to_unit")
     p.add_argument("--label-smoothing", type=float, default=0.2)
+    p.add_argument("--rdrop-alpha", type=_rdrop_alpha_arg, default=0.0,
+                   help="R-Drop: every batch runs twice (duplicated along the batch dimension) and alpha * the "
+                        "symmetric KL of the two dropout passes joins the loss; memory per batch doubles, so "
+                        "halve --max-tokens (0 = off)")
     p.add_argument("--share-decoder-input-output-embed", action="store_true")
     p.add_argument("--dropout", type=float, default=0.1)
     p.add_argument("--attention-dropout", type=float, default=0.1)
@@ -685,7 +732,8 @@ GENERATE_DEFAULTS = {"beam": 5, "max_len_a": 0.0, "max_len_b": 200, "lenpen": 1.
                      "gen_subset": "test", "max_tokens": None, "results_path": None, "path": None,
                      "required_batch_size_multiple": 1, "skip_invalid_size_inputs_valid_test": False,
                      "noise_config_yaml": None, "user_dir": None, "vocoder": None, "fp16": False,
-                     "multitask_config_yaml": None, "data": None}
+                     "multitask_config_yaml": None, "data": None,
+                     "rdrop_alpha": 0.0}     # a training-only regulariser: generation ignores the saved value
 
 
 def build_generate_parser():

@@ -247,6 +247,105 @@ class _LSXentFn(torch.autograd.Function):
         return logits, None, None, None, None, None
 
 
+class _LSXentRdropFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, logits, target, V, eps, pad, alpha, acc, acc_kl):
+        rows, ld = logits.shape
+        out = torch.empty(3, dtype=torch.float32, device=logits.device)
+        lse = K.ls_xent_rdrop_fwd(logits, ld, target, rows, V, eps, pad, alpha, acc, acc_kl, call_out=out)
+        fctx.saved = (logits, target, lse, V, eps, pad, alpha)
+        fctx.set_materialize_grads(False)
+        loss, nll, kl = out[0], out[1], out[2]
+        fctx.mark_non_differentiable(nll, kl)
+        return loss, nll, kl
+
+    @staticmethod
+    def backward(fctx, gloss, gnll, gkl):
+        logits, target, lse, V, eps, pad, alpha = fctx.saved
+        fctx.saved = None
+        rows, ld = logits.shape
+        g = gloss.reshape(1).to(torch.float32).contiguous()
+        # in place over both halves: the logits are dead after this point
+        K.ls_xent_rdrop_bwd(logits, ld, target, rows, V, eps, pad, alpha, lse, g, logits)
+        return logits, None, None, None, None, None, None, None
+
+
+def label_smoothed_ce_rdrop(logits, target_first_half, V, eps, pad, alpha, acc=None):
+    """fairseq RdropLabelSmoothedCrossEntropyCriterion on padded logits [2R, ld] that hold two
+    dropout passes over the same R target rows (row r and row r + R; ``duplicate_batch``):
+    (loss, nll, kl) with kl = compute_kl_loss (the symmetric KL of the two passes summed over the
+    non-pad targets, / 2), nll and the label-smoothed CE summed over all 2R rows and
+    loss = CE + alpha * kl (the differentiable output; kl is already in it).
+    acc: an optional pair of fp32 device views ([2], [1]), e.g. slots of a trainer's step log:
+    {loss, nll} are added to the first, kl to the second."""
+    if not alpha > 0:
+        raise ValueError(f"label_smoothed_ce_rdrop: alpha must be > 0 (got {alpha}); alpha 0 is label_smoothed_ce")
+    acc2, acc_kl = acc if acc is not None else (None, None)
+    return _LSXentRdropFn.apply(logits, target_first_half.reshape(-1), V, eps, pad, float(alpha), acc2, acc_kl)
+
+
+_RDROP_MT_WARNED = [False]
+
+
+def warn_rdrop_multitask(cfg, alpha):
+    """One warning per process when R-Drop meets multitask heads: the heads run on the 2B states
+    with duplicated targets (their losses sum both passes, as fairseq's do), but the KL term
+    fairseq's MultitaskCriterion adds per head is not built."""
+    if alpha > 0 and cfg.get("multitask") and not _RDROP_MT_WARNED[0]:
+        import warnings
+        _RDROP_MT_WARNED[0] = True
+        warnings.warn("--rdrop-alpha with --multitask-config-yaml: the auxiliary heads see both dropout passes, "
+                      "but their own R-Drop KL terms (fairseq MultitaskCriterion) are not implemented")
+
+
+# DeviceBatch fields with one entry per sentence along dim 0, device-side
+_PER_SENTENCE = ("src", "enc_len32", "prev", "tgt_mask", "tgt_len32", "target", "imgs", "img_keymask",
+                 "tgt_lengths32")
+_MT_PER_SENTENCE = ("target", "prev", "tgt_mask", "tgt_len32", "ctc_targets", "ctc_len32")
+
+
+def _dup_into(cache, key, x):
+    """cache[key] = [x; x] along dim 0, written on the current stream into a buffer that is kept
+    (and keeps its address) for as long as x keeps its shape."""
+    if x is None:
+        cache.pop(key, None)
+        return None
+    x = x.contiguous()
+    buf = cache.get(key)
+    if buf is None or buf.shape[1:] != x.shape[1:] or buf.shape[0] != 2 * x.shape[0] or buf.dtype != x.dtype \
+            or buf.device != x.device:
+        buf = cache[key] = torch.empty((2 * x.shape[0], *x.shape[1:]), dtype=x.dtype, device=x.device)
+    torch.cat((x, x), 0, out=buf)
+    return buf
+
+
+def duplicate_batch(batch):
+    """fairseq duplicate_input (--rdrop-alpha > 0): the batch concatenated with itself along the
+    batch dimension, so one forward over 2B sentences gives two dropout passes of every sentence.
+    Every per-sentence device tensor (source features, lengths, prev_output_tokens, target, image
+    features, key masks, the multitask targets) is copied twice on the current stream into buffers
+    cached on ``batch``: no host sync, stable addresses (the copies sit inside a captured step and
+    pick up a ``batch.src`` refreshed by the step's prologue).  The counts (ntokens, nsentences,
+    n_src_frames) stay those of the un-duplicated batch, which is what the criterion logs."""
+    cache = batch.__dict__.setdefault("_rdrop", {})
+    f = {k: _dup_into(cache, k, getattr(batch, k)) for k in _PER_SENTENCE}
+    mt = None
+    if batch.mt is not None:
+        from .multitask import MTBatch
+        mt = {}
+        for name, mb in batch.mt.items():
+            d = MTBatch()
+            for k in MTBatch.__slots__:
+                if not hasattr(mb, k):
+                    continue
+                v = getattr(mb, k)
+                setattr(d, k, _dup_into(cache, f"mt.{name}.{k}", v) if k in _MT_PER_SENTENCE else v)
+            mt[name] = d
+    return DeviceBatch(src_lengths=torch.cat((batch.src_lengths, batch.src_lengths)), Te=batch.Te,
+                       ntokens=batch.ntokens, nsentences=batch.nsentences, n_src_frames=batch.n_src_frames,
+                       mt=mt, **f)
+
+
 def label_smoothed_eval(logits, target, V, eps, pad, stats):
     """Validation scoring of padded logits [rows, ld] (no autograd, no lse, no gradient): stats
     (fp64 device [4]) += {label_smoothed_ce's loss, nll, non-pad targets, teacher-forced argmax

@@ -39,6 +39,8 @@ from .parallel import GradAllReducer, GradNormCheck, all_reduce_scalars
 
 # log slots (all-reduced SUM over ranks every step)
 LOG_LOSS, LOG_NLL, LOG_NTOKENS, LOG_NSENT, LOG_SS_OVER_WORLD = range(5)
+# a sixth slot, present only with cfg["rdrop_alpha"] > 0: the R-Drop KL sum (fairseq rdrop_kl_loss)
+LOG_RDROP_KL = 5
 # per-update increment of the device step seed (odd 64-bit golden-ratio constant)
 STEP_SEED_INC = 0x9E3779B97F4A7C15
 
@@ -88,7 +90,14 @@ class Trainer:
         self.norm_check = GradNormCheck(model.params.flat.device) if world_size > 1 else None
         self.world = world_size
         self.acc = None   # fp32 gradient accumulator (update_freq > 1), allocated on first use
-        self.log = torch.zeros(5, dtype=torch.float32, device=model.params.flat.device)
+        # R-Drop (fairseq --rdrop-alpha): every micro-batch runs duplicated (2B sentences, two
+        # dropout passes) through the pair-KL criterion; 0 = the plain step, launch for launch
+        self.rdrop_alpha = float(self.cfg.get("rdrop_alpha") or 0.0)
+        if self.rdrop_alpha < 0:
+            raise ValueError(f"rdrop_alpha must be >= 0 (got {self.rdrop_alpha})")
+        runtime.warn_rdrop_multitask(self.cfg, self.rdrop_alpha)
+        self.log = torch.zeros(6 if self.rdrop_alpha > 0 else 5, dtype=torch.float32,
+                               device=model.params.flat.device)
         self.vstats = None     # fp64 validation sums (validate), allocated on first use
         self.grad_tap = None   # optional callable(flat fp16 grad) run right before the optimizer (tests)
         # The step's critical path (forward, dgrad chain, optimizer) runs on a high-priority stream
@@ -131,7 +140,9 @@ class Trainer:
     def train_step(self, batches, prologue=None, eager=False, draws=None):
         """batches: one runtime.DeviceBatch or a list of ``update_freq`` micro-batches (fairseq's
         ``samples``).  Returns the device log [loss, nll, ntokens, nsentences, ntokens/world]
-        summed over micro-batches and ranks.
+        summed over micro-batches and ranks; with cfg["rdrop_alpha"] > 0 a sixth value, the R-Drop
+        KL sum, follows (loss and nll are then sums over both dropout passes, the counts stay those
+        of the un-duplicated batches).
 
         prologue: optional callable run at the start of the step (in graph mode it is captured
         with it, e.g. the fbank front end refreshing ``batch.src``).  eager=True (graph mode): run
@@ -218,15 +229,19 @@ class Trainer:
         ntok = sum(int(b.ntokens) for b in batches)
         # the step log in one launch: loss / nll accumulate into it (the LS-CE kernel adds each
         # micro-batch's sums), ntokens / nsentences / sample size per world are known up front
+        A = self.rdrop_alpha
         K.set_f32(self.log, [0.0, 0.0, float(ntok), float(sum(int(b.nsentences) for b in batches)),
-                             float(ntok) / self.world])
+                             float(ntok) / self.world] + ([0.0] if A > 0 else []))
         for i, batch in enumerate(batches):
             last = i == n - 1
             if self.reducer is not None and last:
                 self.reducer.reset()
                 self.reducer.acc = self.acc if n > 1 else None
                 m.grad_ready_hook = self.reducer.ready
-            logits, aux = runtime.model_outputs(m, batch)
+            # R-Drop: the model runs once over the batch concatenated with itself (device-side
+            # copies on this stream, after the prologue refreshed batch.src); the counts above are
+            # the original batch's
+            logits, aux = runtime.model_outputs(m, runtime.duplicate_batch(batch) if A > 0 else batch)
             # The hand-written backward defines every gradient outright: each parameter's gradient
             # is written (not added to) by its backward, or zeroed where a branch skips it
             # (model._zero_grads), so the flat buffer is never cleared as a whole (that fill moved
@@ -235,9 +250,14 @@ class Trainer:
             m.params.await_all()
             if m.params.zero_each_step:
                 m.params.grad.zero_()
-            loss, nll = runtime.label_smoothed_ce(logits, batch.target, cfg["vocab_size"],
-                                                  cfg["label_smoothing"], cfg["padding_idx"],
-                                                  acc=self.log[LOG_LOSS:LOG_NLL + 1])
+            if A > 0:
+                loss, nll, _ = runtime.label_smoothed_ce_rdrop(
+                    logits, batch.target, cfg["vocab_size"], cfg["label_smoothing"], cfg["padding_idx"], A,
+                    acc=(self.log[LOG_LOSS:LOG_NLL + 1], self.log[LOG_RDROP_KL:LOG_RDROP_KL + 1]))
+            else:
+                loss, nll = runtime.label_smoothed_ce(logits, batch.target, cfg["vocab_size"],
+                                                      cfg["label_smoothing"], cfg["padding_idx"],
+                                                      acc=self.log[LOG_LOSS:LOG_NLL + 1])
             del logits
             # multitask heads: loss + sum_t weight_t * loss_t (fairseq MultitaskCriterion); the
             # logged loss stays the main one (fairseq logs multitask losses separately)
