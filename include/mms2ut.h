@@ -1178,6 +1178,34 @@ int mms2ut_rollout_discard_f32(float* x, int nmat, int64_t n, int64_t k, hipStre
 int mms2ut_rollout_chain_f32(const float* a, int B, int L, int T, int normalization, double* sums, float* mask,
                              int32_t* bad, hipStream_t stream);
 
+/* ---------------------------------------------------------------- scoring of generated sequences
+ * The integer kernels behind fairseq-generate's closing BLEU4 / WER line and the reference's
+ * scripts/wer.py (csrc/score.hip).  A batch is n_pairs right-padded int32 rows ref [n_pairs][ld_ref] and
+ * pred [n_pairs][ld_pred] (row strides in elements, also the longest length a row can hold) with int32
+ * lengths per row (clamped to [0, ld]); tokens are arbitrary int32.  One block per pair.  ld_ref, ld_pred
+ * <= MMS_SCORE_MAX_LEN: beyond it the call fails and nothing is launched.  n_pairs = 0 is a no-op.
+ * Integer arithmetic and integer atomic adds only: every run gives the same bits.
+ *
+ * ngram_stats: fairseq libbleu's bleu_add for every pair, added into the persistent device
+ * stats[10] = {reflen, predlen, match1, count1, match2, count2, match3, count3, match4, count4}.
+ * Reference tokens equal to unk (unk < 0: none) become -999; then both sequences are trimmed as libbleu
+ * does: right (end = len - 1; while end > 0 and s[end] is eos or pad: end--; len = end + 1), then left
+ * (leading pad tokens dropped).  reflen += len(ref), predlen += len(pred); for n = 1 .. 4, where
+ * len(pred) >= n: count_n += len(pred) - n + 1, and where also len(ref) >= n: match_n += the sum over
+ * distinct n-grams g of min(occurrences in pred, occurrences in ref), n-grams compared by exact token
+ * equality (libbleu compares 64-bit FNV hashes of them).
+ *
+ * edit_distance: the unit-cost Levenshtein distance of every pair over exactly the given lengths (no
+ * trimming; the reference's unk becomes -999 as above), written to dist[n_pairs] (NULL: not written)
+ * and added into the persistent device totals[2] = {sum of distances, sum of ref lengths}.        */
+#define MMS_SCORE_MAX_LEN 4096
+int mms2ut_ngram_stats(const int32_t* ref, int64_t ld_ref, const int32_t* ref_len, const int32_t* pred,
+                       int64_t ld_pred, const int32_t* pred_len, int n_pairs, int pad, int eos, int unk,
+                       int64_t* stats, hipStream_t stream);
+int mms2ut_edit_distance(const int32_t* ref, int64_t ld_ref, const int32_t* ref_len, const int32_t* pred,
+                         int64_t ld_pred, const int32_t* pred_len, int n_pairs, int unk, int32_t* dist,
+                         int64_t* totals, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,7 @@ class KMeansStepArgs(C.Structure):
 
 VISION_TILE_BYTES, VISION_MAX_SIDE = 49152, 65535         # include/mms2ut.h MMS_VISION_*
 ROLLOUT_MAX_T = 640                                       # include/mms2ut.h MMS_ROLLOUT_MAX_T
+SCORE_MAX_LEN = 4096                                      # include/mms2ut.h MMS_SCORE_MAX_LEN
 
 
 class ImageDesc(C.Structure):
@@ -337,6 +338,8 @@ SIGNATURES = {
     "mms2ut_rollout_probs_f16": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, f32, i32, vp, i64, vp]),
     "mms2ut_rollout_discard_f32": (i32, [vp, i32, i64, i64, vp]),
     "mms2ut_rollout_chain_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "mms2ut_ngram_stats": (i32, [vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, vp, vp]),
+    "mms2ut_edit_distance": (i32, [vp, i64, vp, vp, i64, vp, i32, i32, vp, vp, vp]),
     "mms2ut_layer_arena": (i32, [vp, vp, vp]),
     "mms2ut_layer_scratch": (i32, [vp, f32, vp, vp]),
     "mms2ut_layer_ws": (i32, [vp, vp, vp]),

@@ -19,6 +19,12 @@ with ``{id}`` its 0-based row in ``{subset}.tsv``:
     D-{id}\\t{score}\\t{units}
     P-{id}\\t{positional scores / ln 2, "{:.4f}", space-joined}
 
+The file ends with the ``Translated ...`` line and ``Generate {subset} with beam={beam}: {result}``,
+``{result}`` the string of ``--scoring``'s scorer over the best hypothesis of every sentence
+(scoring.py): ``bleu`` (the default) fairseq's token BLEU4 of the hypothesis' tokens against the target
+row, ``wer`` the unit error rate of the unit strings.  The statistics are accumulated on the device,
+one launch per batch, and read once after the last batch.
+
 There is no ``S-`` line (the speech tasks have no source dictionary).  ``{units}`` is the
 hypothesis without its final ``</s>``.  ``generate-{subset}.unit`` holds column 3 of the best
 ``D-`` line of every sentence in id order: what the reference's
@@ -123,6 +129,7 @@ def load_split(args, task, cfg):
 def main(argv=None):
     from . import generate as G
     from . import manifest as M
+    from . import scoring as S
     given = parse_generate_args(argv)
     ckpt = load_checkpoint(given.path)
     args = merge_generate_args(given, ckpt["args"])
@@ -149,6 +156,8 @@ def main(argv=None):
         out = open(txt_path, "w", buffering=1)
     lines = []
     nsent = ntok = 0
+    pad, eos = ds.tgt_dict.pad(), ds.tgt_dict.eos()
+    scorer = S.build_scorer(args.scoring, pad, eos, M.UNK)
     try:
         cfg = dict(net.cfg, multitask=None)      # the auxiliary heads are not run: no text targets
         torch.cuda.synchronize(dev)
@@ -163,12 +172,16 @@ def main(argv=None):
                 lines += block
                 nsent += 1
                 ntok += len(hypos[i][0]["tokens"])
+            # the first hypothesis of every sentence against its target (--nbest prints more, scores the same)
+            pairs = [S.sentence_pair(args.scoring, t, h[0]["tokens"].tolist(), pad, eos)
+                     for t, h in zip(sample["target"].tolist(), hypos)]
+            scorer.add_batch(*S.upload_pairs([r for r, _ in pairs], [p for _, p in pairs], pad, dev))
         torch.cuda.synchronize(dev)
         dt = max(time.perf_counter() - t0, 1e-9)
         log.info("%d batches, step graph captured %d times", len(batches), G.graph_captures() - captures0)
         tail = ["Translated {:,} sentences ({:,} tokens) in {:.1f}s ({:.2f} sentences/s, {:.2f} tokens/s)".format(
                     nsent, ntok, dt, nsent / dt, ntok / dt),
-                f"Generate {args.gen_subset} with beam={args.beam}: unit BLEU is not computed"]
+                f"Generate {args.gen_subset} with beam={args.beam}: {scorer.result_string()}"]
         print("\n".join(tail), file=out)
     finally:
         if out is not sys.stdout:

@@ -2264,4 +2264,51 @@ def rollout_chain(a, normalization="reference"):
     return mask, bad
 
 
+# ============================================================================ scoring (BLEU n-gram statistics, WER)
+
+SCORE_MAX_LEN = _lib.SCORE_MAX_LEN
+
+
+def _score_pairs(name, ref, ref_len, pred, pred_len):
+    """The shape checks both scoring kernels share -> n_pairs.  The length limit is the library's check."""
+    for t, l, what in ((ref, ref_len, "ref"), (pred, pred_len, "pred")):
+        _chk(t, torch.int32)
+        _chk(l, torch.int32)
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) != t.shape[1]):
+            raise ValueError(f"{name}: {what} must be contiguous int32 [n_pairs, ld], got {tuple(t.shape)}")
+        if l.dim() != 1 or l.numel() != t.shape[0] or not l.is_contiguous():
+            raise ValueError(f"{name}: {what}_len must be contiguous int32 [{t.shape[0]}], got {tuple(l.shape)}")
+    if ref.shape[0] != pred.shape[0]:
+        raise ValueError(f"{name}: {ref.shape[0]} references against {pred.shape[0]} predictions")
+    return ref.shape[0]
+
+
+def ngram_stats(ref, ref_len, pred, pred_len, stats, pad, eos, unk=-1):
+    """fairseq libbleu's bleu_add over a batch: right-padded int32 ref [n, ld_ref] / pred [n, ld_pred] with
+    int32 lengths [n] (unk in the reference -> -999, libbleu's trims, exact n-gram matching) added into the
+    device int64 stats[10] = {reflen, predlen, match1, count1, ..., match4, count4}.  Launch only: no host
+    read.  Rows hold at most SCORE_MAX_LEN tokens (the library's error beyond)."""
+    n = _score_pairs("ngram_stats", ref, ref_len, pred, pred_len)
+    _chk(stats, torch.int64)
+    if stats.numel() != 10 or not stats.is_contiguous():
+        raise ValueError(f"ngram_stats: stats must be contiguous int64 [10], got {tuple(stats.shape)}")
+    call("mms2ut_ngram_stats", ref.data_ptr(), ref.shape[1], ref_len.data_ptr(), pred.data_ptr(), pred.shape[1],
+         pred_len.data_ptr(), n, int(pad), int(eos), -1 if unk is None else int(unk), stats.data_ptr(), _s())
+    return stats
+
+
+def edit_distance(ref, ref_len, pred, pred_len, totals, unk=-1, *, want_dist=False):
+    """Unit-cost Levenshtein distance of every pair of a batch (layout as ngram_stats; exactly the given
+    lengths, no trimming; unk in the reference -> -999), added into the device int64 totals[2] = {sum of
+    distances, sum of reference lengths}.  -> int32 [n] distances with want_dist, else None.  Launch only."""
+    n = _score_pairs("edit_distance", ref, ref_len, pred, pred_len)
+    _chk(totals, torch.int64)
+    if totals.numel() != 2 or not totals.is_contiguous():
+        raise ValueError(f"edit_distance: totals must be contiguous int64 [2], got {tuple(totals.shape)}")
+    dist = torch.empty(n, dtype=torch.int32, device=ref.device) if want_dist else None
+    call("mms2ut_edit_distance", ref.data_ptr(), ref.shape[1], ref_len.data_ptr(), pred.data_ptr(), pred.shape[1],
+         pred_len.data_ptr(), n, -1 if unk is None else int(unk), _p(dist), totals.data_ptr(), _s())
+    return dist
+
+
 __all__ = [n for n in dir() if not n.startswith("_")] + ["math"]

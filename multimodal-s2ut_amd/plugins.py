@@ -733,7 +733,9 @@ GENERATE_DEFAULTS = {"beam": 5, "max_len_a": 0.0, "max_len_b": 200, "lenpen": 1.
                      "required_batch_size_multiple": 1, "skip_invalid_size_inputs_valid_test": False,
                      "noise_config_yaml": None, "user_dir": None, "vocoder": None, "fp16": False,
                      "multitask_config_yaml": None, "data": None,
-                     "rdrop_alpha": 0.0}     # a training-only regulariser: generation ignores the saved value
+                     "rdrop_alpha": 0.0,     # a training-only regulariser: generation ignores the saved value
+                     "scoring": "bleu"}      # fairseq's default scorer (scoring.py)
+GENERATE_SCORERS = ("bleu", "wer")
 
 
 def build_generate_parser():
@@ -765,6 +767,8 @@ def build_generate_parser():
     p.add_argument("--min-len", type=int)
     p.add_argument("--nbest", type=int)
     p.add_argument("--results-path")
+    p.add_argument("--scoring", help="what the closing line reports over the best hypotheses: bleu (token BLEU4, "
+                                     "the default) or wer")
     p.add_argument("--seed", type=int)
     # accepted for command-line compatibility, no effect
     p.add_argument("--user-dir")
@@ -779,6 +783,9 @@ def parse_generate_args(argv=None):
     given = p.parse_args(argv)
     if getattr(given, "required_batch_size_multiple", 1) != 1:
         p.error("--required-batch-size-multiple must be 1 (batches are not rounded to a multiple)")
+    if getattr(given, "scoring", "bleu") not in GENERATE_SCORERS:
+        raise SystemExit(f"mms2ut-generate: unknown --scoring {given.scoring!r}; the scorers are "
+                         f"{' and '.join(GENERATE_SCORERS)}")
     return given
 
 
