@@ -630,7 +630,8 @@ int mms2ut_noise_mix_f32(float* wave, const int64_t* wave_off, int B,
  * Activations are time-major fp16 rows [T, C]; C is a multiple of 8 and >= 8 everywhere (16-byte
  * rows), anything else is refused.  All accumulation is fp32.
  *
- * mms2ut_conv1d_tm: implicit-GEMM dilated Conv1d (no im2col image), one launch:
+ * mms2ut_conv1d_tm: implicit-GEMM dilated Conv1d (no im2col image; the tile of csrc/conv1d_tm.h,
+ * which mms2ut_asr_conv runs too), one launch:
  *   v[q, co]  = bias[co] + sum_{j < taps, ci} in(x[q + j*dil - pad, ci]) * W[co, ci, j]
  *               (rows outside [0, T_in) read as zeros; in = leaky-ReLU(in_slope) if in_act)
  *   v        += res[q, co]                       if res
@@ -761,7 +762,8 @@ int mms2ut_wave_stats(const float* x, int64_t n, float eps, double* ws, float* s
 int mms2ut_asr_conv0(const float* x, int64_t n, const float* stats, const float* w, const float* bias,
                      const float* ln_g, const float* ln_b, float eps, int k, int stride, int C, void* y,
                      int64_t ldy, hipStream_t stream);
-/* Implicit-GEMM Conv1d with a stride and groups (no im2col image), one launch; group g reads the
+/* Implicit-GEMM Conv1d with a stride and groups (no im2col image; the tile of csrc/conv1d_tm.h,
+ * which mms2ut_conv1d_tm runs too), one launch; group g reads the
  * columns [g Cin, (g + 1) Cin) of x and writes the columns [g Cout, (g + 1) Cout) of y:
  *   v[q, co] = bias[co] + sum_{j < taps, ci} x[q * stride + j - pad, ci] * W[co, ci, j]
  *              (rows outside [0, T_in) read as zeros)

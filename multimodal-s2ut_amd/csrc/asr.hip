@@ -11,8 +11,8 @@
 //                      read, Conv1d(1 -> C, k taps, stride s) + bias, LayerNorm over the C channels of
 //                      each frame, GELU, fp16 [T0, C] out.  16 frames per block, one thread per channel
 //                      pair; memory bound.
-//   asr_conv           implicit-GEMM Conv1d on v_mfma_f32_16x16x32_f16 with a stride and groups: the
-//                      sibling of vocoder.hip's conv1d_tm_kernel (same weight image, same tiling, same
+//   asr_conv           implicit-GEMM Conv1d with a stride and groups: the tile of conv1d_tm.h, which
+//                      vocoder.hip's conv1d_tm_kernel runs too (one weight image, one tiling, one
 //                      split of K over the waves when the grid is small).  The operand row of output q,
 //                      tap j is input row stride * q + j - pad, read from the block's staged rows in
 //                      LDS; the reduction runs over (tap, cin).  blockIdx.z is the group.  Epilogue:
@@ -25,12 +25,9 @@
 //   ctc_greedy         one block per utterance: bias + per-frame argmax over the fp32 logits (lowest
 //                      index on ties), then a block prefix sum compacts the ids that start a run and
 //                      are not the blank.  Only ids, a count and a non-finite flag leave the device.
-#include "common.h"
-#include "../../include/mms2ut.h"
+#include "conv1d_tm.h"
 
 namespace {
-
-MMS_DEV float gelu_erf(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752f)); }
 
 // ---------------------------------------------------------------------------------------------
 // utterance statistics
@@ -159,137 +156,47 @@ __global__ void __launch_bounds__(A0_THREADS) asr_conv0_kernel(
 // ---------------------------------------------------------------------------------------------
 // strided / grouped implicit-GEMM Conv1d
 // ---------------------------------------------------------------------------------------------
-constexpr int AC_TN = 64;         // output channels per block (up to 4 MFMA row tiles)
-constexpr int AC_CHUNK = MMS_VOC_CIN_CHUNK;
-constexpr int AC_LD = AC_CHUNK + 8;   // LDS row stride in halves: 144 B, rows 16-byte aligned
-constexpr int AC_THREADS = 256;
-constexpr int AC_GROUP = 4;       // K-steps whose weight fragments are loaded together
-constexpr int AC_SPLIT_MIN_STEPS = 4, AC_SPLIT_MAX_BLOCKS = 256;
 constexpr int AC_ROWS = MMS_ASR_CONV_MAX_ROWS;        // staged rows of a 128-position block
 constexpr int AC_ROWS_SPLIT = AC_ROWS - 96;           // of a 32-position block: (32 - 128) * stride fewer, stride >= 1
 
-// SPLITK false: the block owns 128 positions, wave w rows [32 w, 32 w + 32), every wave walks all
-// K-steps.  SPLITK true: the block owns 32 positions, wave w takes K-steps w, w + 4, ... and wave 0
-// adds the four partial tiles (in wave order) before the epilogue.
+// what conv1d_tm_tile needs of one group (blockIdx.z)
+struct AsrConvView {
+  const mms2ut_asr_conv_args& a;
+  const h16* x;
+  const h16* w;
+  const float* bias;
+  const h16* res;
+  h16* y;
+  const int T_in, nq;
+  const long ldx;
+  MMS_DEV AsrConvView(const mms2ut_asr_conv_args& a_, int grp)
+      : a(a_), x(reinterpret_cast<const h16*>(a_.x) + (long)grp * a_.Cin),
+        w(reinterpret_cast<const h16*>(a_.w) + (long)grp * a_.w_group),
+        bias(a_.bias ? a_.bias + (long)grp * a_.Cout : nullptr),
+        res(a_.res ? reinterpret_cast<const h16*>(a_.res) + (long)grp * a_.Cout : nullptr),
+        y(reinterpret_cast<h16*>(a_.y) + (long)grp * a_.Cout), T_in(a_.T_in), nq(a_.T_out), ldx(a_.ldx) {}
+  MMS_DEV int rows(int TM) const { return (TM - 1) * a.stride + a.taps; }  // <= the LDS rows (host check)
+  MMS_DEV long row0(int q0) const { return (long)q0 * a.stride - a.pad; }
+  MMS_DEV int lds_row(int p, int j) const { return p * a.stride + j; }
+  MMS_DEV h16x8 stage(h16x8 v) const { return v; }
+  MMS_DEV void emit(int q, int co, f32x4 v) const {
+    if (res) {
+      const h16x4 rv = *reinterpret_cast<const h16x4*>(res + (long)q * a.ldres + co);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (float)rv[e] + gelu_erf(v[e]);
+    } else if (a.gelu) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
+    }
+    conv_store4(y + (long)q * a.ldy + co, v);
+  }
+};
+
 template <bool SPLITK>
-__global__ void __launch_bounds__(AC_THREADS) asr_conv_kernel(const mms2ut_asr_conv_args a) {
-  constexpr int TM = SPLITK ? 32 : 128;
-  __shared__ __attribute__((aligned(16))) h16 xs[(SPLITK ? AC_ROWS_SPLIT : AC_ROWS) * AC_LD];
-  __shared__ f32x4 red[SPLITK ? 3 * 8 * 64 : 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l15 = lane & 15, lk = (lane >> 4) * 8;
-  const int q0 = blockIdx.x * TM, co0 = blockIdx.y * AC_TN, grp = blockIdx.z;
-  const int CoutP = (a.Cout + 15) & ~15;
-  const int nb = min(AC_TN / 16, (CoutP - co0) / 16);
-  const h16* __restrict__ x = reinterpret_cast<const h16*>(a.x) + (long)grp * a.Cin;
-  const h16* __restrict__ w = reinterpret_cast<const h16*>(a.w) + (long)grp * a.w_group;
-  const int rows = (TM - 1) * a.stride + a.taps;          // <= the LDS rows (host check)
-  const long row0 = (long)q0 * a.stride - a.pad;
-  const int wrow = SPLITK ? 0 : wave * 32;
-  const int s_first = SPLITK ? wave : 0, s_stride = SPLITK ? 4 : 1;
-
-  f32x4 acc[AC_TN / 16][2];
-#pragma unroll
-  for (int g = 0; g < AC_TN / 16; ++g)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) acc[g][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  int sbase = 0;
-  for (int c0 = 0; c0 < a.Cin; c0 += AC_CHUNK) {
-    const int cw = min(AC_CHUNK, a.Cin - c0), cv = cw >> 3;
-    __syncthreads();                                      // the previous slice's reads are done
-    for (int u = tid; u < rows * cv; u += AC_THREADS) {
-      const int rr = u / cv, cc = (u - rr * cv) * 8;
-      const long row = row0 + rr;
-      h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (row >= 0 && row < a.T_in) v = *reinterpret_cast<const h16x8*>(x + row * a.ldx + c0 + cc);
-      *reinterpret_cast<h16x8*>(xs + rr * AC_LD + cc) = v;
-    }
-    __syncthreads();
-    const int nsteps = (a.taps * cw + 31) >> 5;
-    for (int s0 = s_first; s0 < nsteps; s0 += AC_GROUP * s_stride) {
-      h16x8 wf[AC_GROUP][AC_TN / 16];
-#pragma unroll
-      for (int u = 0; u < AC_GROUP; ++u) {
-        const int s = s0 + u * s_stride;
-        const h16* wp = w + ((long)(sbase + s) * CoutP + co0 + l15) * 32 + lk;
-#pragma unroll
-        for (int g = 0; g < AC_TN / 16; ++g)
-          if (s < nsteps && g < nb) wf[u][g] = *reinterpret_cast<const h16x8*>(wp + g * 16 * 32);
-      }
-#pragma unroll
-      for (int u = 0; u < AC_GROUP; ++u) {
-        const int s = s0 + u * s_stride;
-        if (s < nsteps) {
-          const int kk = s * 32 + lk;
-          const int j = kk / cw, c = kk - j * cw;
-          const bool valid = j < a.taps;                  // the K tail of the last step: zero weights too
-          h16x8 xf[2];
-#pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            xf[f] = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            if (valid) xf[f] = *reinterpret_cast<const h16x8*>(xs + ((wrow + f * 16 + l15) * a.stride + j) * AC_LD + c);
-          }
-#pragma unroll
-          for (int g = 0; g < AC_TN / 16; ++g)
-            if (g < nb) {
-#pragma unroll
-              for (int f = 0; f < 2; ++f)
-                acc[g][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][g], xf[f], acc[g][f], 0, 0, 0);
-            }
-        }
-      }
-    }
-    sbase += nsteps;
-  }
-
-  if (SPLITK) {
-    if (wave > 0) {
-#pragma unroll
-      for (int g = 0; g < AC_TN / 16; ++g)
-#pragma unroll
-        for (int f = 0; f < 2; ++f) red[((wave - 1) * 8 + g * 2 + f) * 64 + lane] = acc[g][f];
-    }
-    __syncthreads();
-    if (wave > 0) return;
-#pragma unroll
-    for (int wv = 0; wv < 3; ++wv)
-#pragma unroll
-      for (int g = 0; g < AC_TN / 16; ++g)
-#pragma unroll
-        for (int f = 0; f < 2; ++f) acc[g][f] += red[(wv * 8 + g * 2 + f) * 64 + lane];
-  }
-
-  // D[row = cout (lane>>4)*4 + e][col = position lane&15]
-  h16* __restrict__ y = reinterpret_cast<h16*>(a.y) + (long)grp * a.Cout;
-  const h16* __restrict__ res = a.res ? reinterpret_cast<const h16*>(a.res) + (long)grp * a.Cout : nullptr;
-  const float* __restrict__ bias = a.bias ? a.bias + (long)grp * a.Cout : nullptr;
-#pragma unroll
-  for (int g = 0; g < AC_TN / 16; ++g) {
-    if (g >= nb) continue;
-    const int co = co0 + g * 16 + (lane >> 4) * 4;
-    if (co >= a.Cout) continue;                           // Cout is a multiple of 8: whole groups of 4
-    f32x4 b = {0.f, 0.f, 0.f, 0.f};
-    if (bias) b = *reinterpret_cast<const f32x4*>(bias + co);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const int q = q0 + wrow + f * 16 + l15;
-      if (q >= a.T_out) continue;
-      f32x4 v = acc[g][f] + b;
-      if (res) {
-        const h16x4 rv = *reinterpret_cast<const h16x4*>(res + (long)q * a.ldres + co);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (float)rv[e] + gelu_erf(v[e]);
-      } else if (a.gelu) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-      }
-      h16x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (h16)v[e];
-      *reinterpret_cast<h16x4*>(y + (long)q * a.ldy + co) = o;
-    }
-  }
+__global__ void __launch_bounds__(CT_THREADS) asr_conv_kernel(const mms2ut_asr_conv_args a) {
+  __shared__ __attribute__((aligned(16))) h16 xs[(SPLITK ? AC_ROWS_SPLIT : AC_ROWS) * CT_LD];
+  __shared__ f32x4 red[conv_red_elems(SPLITK)];
+  conv1d_tm_tile<SPLITK>(AsrConvView(a, blockIdx.z), a.Cin, a.Cout, a.taps, xs, red);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -435,8 +342,10 @@ extern "C" int mms2ut_asr_conv0(const float* x, int64_t n, const float* stats, c
 
 extern "C" int mms2ut_asr_conv(const mms2ut_asr_conv_args* a, hipStream_t s) {
   MMS_REQUIRE(a, "asr_conv: null args");
-  MMS_REQUIRE(a->Cin >= 8 && a->Cin % 8 == 0 && a->Cout >= 8 && a->Cout % 8 == 0,
-              "asr_conv: channel widths per group must be multiples of 8 and >= 8 (Cin %d, Cout %d)", a->Cin, a->Cout);
+  const long wx = (long)a->groups * a->Cin, wy = (long)a->groups * a->Cout;
+  if (int rc = conv_check("asr_conv", " per group", a->Cin, a->Cout, a->x, a->ldx, wx, a->w, a->bias, a->y, a->ldy,
+                          a->res, a->ldres, wy))
+    return rc;
   MMS_REQUIRE(a->taps >= 1 && a->stride >= 1 && a->pad >= 0 && a->groups >= 1 && a->groups <= 65535,
               "asr_conv: taps, stride, groups >= 1 and pad >= 0");
   MMS_REQUIRE(127L * a->stride + a->taps <= AC_ROWS, "asr_conv: 127 * stride + taps must be at most %d (stride %d, taps %d)",
@@ -445,25 +354,8 @@ extern "C" int mms2ut_asr_conv(const mms2ut_asr_conv_args* a, hipStream_t s) {
   // every output reads rows inside [-pad, T_in + pad): nothing but the padding is made up
   MMS_REQUIRE((long)(a->T_out - 1) * a->stride + a->taps <= (long)a->T_in + 2L * a->pad,
               "asr_conv: %d outputs need more than the %d input rows and padding %d", a->T_out, a->T_in, a->pad);
-  MMS_REQUIRE(a->x && a->w && a->y, "asr_conv: null buffer");
-  const long wx = (long)a->groups * a->Cin, wy = (long)a->groups * a->Cout;
-  MMS_REQUIRE(a->ldx >= wx && a->ldx % 8 == 0 && a->ldy >= wy && a->ldy % 4 == 0 &&
-                  (!a->res || (a->ldres >= wy && a->ldres % 4 == 0)),
-              "asr_conv: row strides must cover the width and keep rows 16-byte (x) / 8-byte (y, res) aligned");
-  MMS_REQUIRE(((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->w & 15) == 0 && ((uintptr_t)a->y & 7) == 0 &&
-                  ((uintptr_t)a->res & 7) == 0 && ((uintptr_t)a->bias & 15) == 0 && a->w_group % 8 == 0,
-              "asr_conv: misaligned buffer");
-  const int cy = (a->Cout + AC_TN - 1) / AC_TN;
-  MMS_REQUIRE(cy <= 65535, "asr_conv: grid too large");
-  // the rule of vocoder.hip's conv_launch: few blocks and a long reduction -> the waves split K
-  long steps = 0;
-  for (int c0 = 0; c0 < a->Cin; c0 += AC_CHUNK) steps += ((long)a->taps * min(AC_CHUNK, a->Cin - c0) + 31) / 32;
-  const long blocks128 = (long)((a->T_out + 127) / 128) * cy * a->groups;
-  if (steps >= AC_SPLIT_MIN_STEPS && blocks128 < AC_SPLIT_MAX_BLOCKS) {
-    hipLaunchKernelGGL(asr_conv_kernel<true>, dim3((a->T_out + 31) / 32, cy, a->groups), dim3(AC_THREADS), 0, s, *a);
-  } else {
-    hipLaunchKernelGGL(asr_conv_kernel<false>, dim3((a->T_out + 127) / 128, cy, a->groups), dim3(AC_THREADS), 0, s, *a);
-  }
+  MMS_REQUIRE(a->w_group % 8 == 0, "asr_conv: misaligned buffer");
+  conv_tm_launch(asr_conv_kernel<true>, asr_conv_kernel<false>, *a, a->Cin, a->Cout, a->taps, a->T_out, a->groups, s);
   return mms::check_launch("asr_conv");
 }
 

@@ -190,5 +190,8 @@ MMS_DEV double wave_sum_d(double v) {
   return v;
 }
 
+// torch F.gelu (approximate='none'): 0.5 z (1 + erf(z / sqrt 2))
+MMS_DEV float gelu_erf(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752f)); }
+
 MMS_DEV float h2f(h16 x) { return (float)x; }
 MMS_DEV h16 f2h(float x) { return (h16)x; }

@@ -87,8 +87,7 @@ MMS_DEV h16x8 read_frag(const char* lds, int sub, int kk, int lane) {
 }
 
 MMS_DEV float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
-// torch F.gelu (approximate='none'): 0.5 z (1 + erf(z / sqrt 2)) and its derivative
-MMS_DEV float gelu_(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752f)); }
+// the derivative of common.h's gelu_erf
 MMS_DEV float gelu_grad_(float z) {
   return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.39894228040143268f * __expf(-0.5f * z * z);
 }
@@ -141,7 +140,7 @@ MMS_DEV float epi_element(float x, float a, float a2, bool keep, float dscale, h
   if (EPI == MMS_EPI_F16_ACC) return a + x;
   if (EPI == MMS_EPI_GELU_DROP) {
     o2 = (h16)x;
-    return keep ? gelu_((float)o2) * dscale : 0.f;
+    return keep ? gelu_erf((float)o2) * dscale : 0.f;
   }
   if (EPI == MMS_EPI_GELU_DROP_BWD) return keep ? x * dscale * gelu_grad_(a) : 0.f;
   return x;
@@ -270,7 +269,7 @@ MMS_DEV void epilogue_store(const GemmP& P, void* Cz, const h16* auxz, int m, in
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       zh[r] = (h16)x[r];
-      o[r] = keep[r] ? gelu_((float)zh[r]) * dscale : 0.f;
+      o[r] = keep[r] ? gelu_erf((float)zh[r]) * dscale : 0.f;
     }
     h16* z_row = P.out2 + (long)m * P.ldo2;
     if (full) {
@@ -376,7 +375,7 @@ MMS_DEV void epilogue_store8(const GemmP& P, void* Cz, const h16* auxz, int m, i
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       zv[r] = (h16)x[r];
-      o[r] = keep[r] ? gelu_((float)zv[r]) * dscale : 0.f;
+      o[r] = keep[r] ? gelu_erf((float)zv[r]) * dscale : 0.f;
     }
     *reinterpret_cast<h16x8*>(P.out2 + (long)m * P.ldo2 + n) = zv;
   } else if (EPI == MMS_EPI_GELU_DROP_BWD) {

@@ -33,8 +33,6 @@
 
 namespace {
 
-MMS_DEV float gelu_erf(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752f)); }
-
 // ---------------------------------------------------------------------------------------------
 // layer 0 with GroupNorm over time
 // ---------------------------------------------------------------------------------------------

@@ -3,19 +3,12 @@
 // Activations are time-major fp16 rows [T, C].  A convolution tap is then a row-shifted read and the
 // GEMM reduction runs over (tap, cin); there is no im2col image anywhere.
 //
-//   conv1d_tm_kernel   implicit-GEMM Conv1d on v_mfma_f32_16x16x32_f16.  One block owns 128 output
-//                      positions (32 where the waves split K, see conv_launch) x up to 64 output
-//                      channels.  Per 64-wide slice of Cin it stages the rows
-//                      [q0 - pad, q0 - pad + positions + (taps-1)*dil) once into LDS (input
-//                      leaky-ReLU applied on the way, rows outside [0, T_in) as zeros: the padding
-//                      at both sequence ends), then every K-step of 32 reads its operand as one
-//                      16-byte LDS read per lane at row + tap*dil.  The weights were repacked at
-//                      load into the MFMA A-operand image ([K-step][cout][32]), so a lane's fragment
-//                      is one 16-byte global read, shared through L1/L2 by all blocks.  The product
-//                      is computed transposed (A = weights, B = activations): a lane then holds four
-//                      consecutive output channels of one position and writes them with one 8-byte
-//                      store.  Epilogue in the same launch: + bias, + residual row, leaky-ReLU,
-//                      y = scale * v or y += scale * v.
+//   conv1d_tm_kernel   implicit-GEMM Conv1d with a dilation: the tile of conv1d_tm.h (128 output
+//                      positions, or 32 where the waves split K, x up to 64 output channels) over the
+//                      staged rows [q0 - pad, q0 - pad + positions + (taps-1)*dil), input leaky-ReLU
+//                      applied on the way into LDS; output q reads tap j at row q + j*dil.  Epilogue
+//                      in the same launch: + bias, + residual row, leaky-ReLU, y = scale * v or
+//                      y += scale * v.
 //   the same kernel    runs ConvTranspose1d as a polyphase convolution: output phase r = (t' + p)
 //                      mod u is an ordinary convolution over ceil(k/u) taps with its own weight
 //                      image (blockIdx.z = r) whose output rows are q*u + r - p.
@@ -24,18 +17,11 @@
 //                      durations (binary search), or src = t' without durations.
 //   var_pred_layer     one layer of the duration predictor, all fp32: Conv1d + ReLU + LayerNorm,
 //                      and on the last layer the projection, exp, round-half-even and clamp.
-#include "common.h"
-#include "../../include/mms2ut.h"
+#include "conv1d_tm.h"
 
 namespace {
 
-constexpr int VC_TN = 64;         // output channels per block (up to 4 MFMA row tiles)
-constexpr int VC_CHUNK = MMS_VOC_CIN_CHUNK;
 constexpr int VC_HALO = MMS_VOC_MAX_SPAN;
-constexpr int VC_LD = VC_CHUNK + 8;   // LDS row stride in halves: 144 B, rows 16-byte aligned
-constexpr int VC_THREADS = 256;
-constexpr int VC_GROUP = 4;       // K-steps whose weight fragments are loaded together
-constexpr int VC_SPLIT_MIN_STEPS = 4, VC_SPLIT_MAX_BLOCKS = 256;    // when the waves split K (conv_launch)
 
 MMS_DEV h16x8 lrelu8(h16x8 v, float slope) {
 #pragma unroll
@@ -46,173 +32,66 @@ MMS_DEV h16x8 lrelu8(h16x8 v, float slope) {
   return v;
 }
 
-// SPLITK false: the block owns 128 positions, wave w rows [32 w, 32 w + 32), every wave walks all
-// K-steps.  SPLITK true: the block owns 32 positions, wave w takes K-steps w, w + 4, ... and wave 0
-// adds the four partial tiles (in wave order) before the epilogue.
+// what conv1d_tm_tile needs of one output phase (blockIdx.z)
+struct VocConvView {
+  const mms2ut_conv1d_tm_args& a;
+  const int phase;
+  const h16* x;
+  const h16* w;
+  const float* bias;
+  const int T_in, nq;
+  const long ldx;
+  MMS_DEV VocConvView(const mms2ut_conv1d_tm_args& a_, int z)
+      : a(a_), phase(z), x(reinterpret_cast<const h16*>(a_.x)),
+        w(reinterpret_cast<const h16*>(a_.w) + (long)z * a_.w_phase), bias(a_.bias), T_in(a_.T_in), nq(a_.nq),
+        ldx(a_.ldx) {}
+  MMS_DEV int rows(int TM) const { return TM + (a.taps - 1) * a.dil; }     // <= TM + VC_HALO (host check)
+  MMS_DEV int row0(int q0) const { return q0 - a.pad; }
+  MMS_DEV int lds_row(int p, int j) const { return p + j * a.dil; }
+  MMS_DEV h16x8 stage(h16x8 v) const { return a.in_act ? lrelu8(v, a.in_slope) : v; }
+  MMS_DEV void emit(int q, int co, f32x4 v) const {
+    const long orow = (long)q * a.ostride + phase + a.ooff;
+    if (orow < 0 || orow >= a.T_out) return;
+    const h16* __restrict__ res = reinterpret_cast<const h16*>(a.res);
+    if (res) {
+      const h16x4 rv = *reinterpret_cast<const h16x4*>(res + orow * a.ldres + co);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] += (float)rv[e];
+    }
+    if (a.out_act) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a.out_slope;
+    }
+    h16* yp = reinterpret_cast<h16*>(a.y) + orow * a.ldy + co;
+    if (a.acc != MMS_VOC_ACC_NONE) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] *= a.scale;
+      if (a.acc == MMS_VOC_ACC_ADD) {
+        const h16x4 pv = *reinterpret_cast<const h16x4*>(yp);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] += (float)pv[e];
+      }
+    }
+    conv_store4(yp, v);
+  }
+};
+
 template <bool SPLITK>
-__global__ void __launch_bounds__(VC_THREADS) conv1d_tm_kernel(const mms2ut_conv1d_tm_args a) {
-  constexpr int TM = SPLITK ? 32 : 128;
-  __shared__ __attribute__((aligned(16))) h16 xs[(TM + VC_HALO) * VC_LD];
-  __shared__ f32x4 red[SPLITK ? 3 * 8 * 64 : 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l15 = lane & 15, lk = (lane >> 4) * 8;
-  const int q0 = blockIdx.x * TM, co0 = blockIdx.y * VC_TN, phase = blockIdx.z;
-  const int CoutP = (a.Cout + 15) & ~15;
-  const int nb = min(VC_TN / 16, (CoutP - co0) / 16);
-  const h16* __restrict__ x = reinterpret_cast<const h16*>(a.x);
-  const h16* __restrict__ w = reinterpret_cast<const h16*>(a.w) + (long)phase * a.w_phase;
-  const int rows = TM + (a.taps - 1) * a.dil;             // <= TM + VC_HALO (host check)
-  const int wrow = SPLITK ? 0 : wave * 32;
-  const int s_first = SPLITK ? wave : 0, s_stride = SPLITK ? 4 : 1;
-
-  f32x4 acc[VC_TN / 16][2];
-#pragma unroll
-  for (int g = 0; g < VC_TN / 16; ++g)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) acc[g][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  int sbase = 0;
-  for (int c0 = 0; c0 < a.Cin; c0 += VC_CHUNK) {
-    const int cw = min(VC_CHUNK, a.Cin - c0), cv = cw >> 3;
-    __syncthreads();                                      // the previous slice's reads are done
-    for (int u = tid; u < rows * cv; u += VC_THREADS) {
-      const int rr = u / cv, cc = (u - rr * cv) * 8;
-      const int row = q0 + rr - a.pad;
-      h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (row >= 0 && row < a.T_in) {
-        v = *reinterpret_cast<const h16x8*>(x + (long)row * a.ldx + c0 + cc);
-        if (a.in_act) v = lrelu8(v, a.in_slope);
-      }
-      *reinterpret_cast<h16x8*>(xs + rr * VC_LD + cc) = v;
-    }
-    __syncthreads();
-    const int nsteps = (a.taps * cw + 31) >> 5;
-    // The weights of a launch are cold and every block walks them in step, so a K-step's fragment
-    // load costs a full memory latency: VC_GROUP steps' loads are issued before their MFMAs.
-    for (int s0 = s_first; s0 < nsteps; s0 += VC_GROUP * s_stride) {
-      h16x8 wf[VC_GROUP][VC_TN / 16];
-#pragma unroll
-      for (int u = 0; u < VC_GROUP; ++u) {
-        const int s = s0 + u * s_stride;
-        const h16* wp = w + ((long)(sbase + s) * CoutP + co0 + l15) * 32 + lk;
-#pragma unroll
-        for (int g = 0; g < VC_TN / 16; ++g)
-          if (s < nsteps && g < nb) wf[u][g] = *reinterpret_cast<const h16x8*>(wp + g * 16 * 32);
-      }
-#pragma unroll
-      for (int u = 0; u < VC_GROUP; ++u) {
-        const int s = s0 + u * s_stride;
-        if (s < nsteps) {
-          const int kk = s * 32 + lk;
-          const int j = kk / cw, c = kk - j * cw;
-          const bool valid = j < a.taps;                  // the K tail of the last step: zero weights too
-          h16x8 xf[2];
-#pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            xf[f] = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            if (valid) xf[f] = *reinterpret_cast<const h16x8*>(xs + (wrow + f * 16 + l15 + j * a.dil) * VC_LD + c);
-          }
-#pragma unroll
-          for (int g = 0; g < VC_TN / 16; ++g)
-            if (g < nb) {
-#pragma unroll
-              for (int f = 0; f < 2; ++f)
-                acc[g][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][g], xf[f], acc[g][f], 0, 0, 0);
-            }
-        }
-      }
-    }
-    sbase += nsteps;
-  }
-
-  if (SPLITK) {
-    if (wave > 0) {
-#pragma unroll
-      for (int g = 0; g < VC_TN / 16; ++g)
-#pragma unroll
-        for (int f = 0; f < 2; ++f) red[((wave - 1) * 8 + g * 2 + f) * 64 + lane] = acc[g][f];
-    }
-    __syncthreads();
-    if (wave > 0) return;
-#pragma unroll
-    for (int wv = 0; wv < 3; ++wv)
-#pragma unroll
-      for (int g = 0; g < VC_TN / 16; ++g)
-#pragma unroll
-        for (int f = 0; f < 2; ++f) acc[g][f] += red[(wv * 8 + g * 2 + f) * 64 + lane];
-  }
-
-  // D[row = cout (lane>>4)*4 + e][col = position lane&15]
-  h16* __restrict__ y = reinterpret_cast<h16*>(a.y);
-  const h16* __restrict__ res = reinterpret_cast<const h16*>(a.res);
-#pragma unroll
-  for (int g = 0; g < VC_TN / 16; ++g) {
-    if (g >= nb) continue;
-    const int co = co0 + g * 16 + (lane >> 4) * 4;
-    if (co >= a.Cout) continue;                           // Cout is a multiple of 8: whole groups of 4
-    f32x4 b = {0.f, 0.f, 0.f, 0.f};
-    if (a.bias) b = *reinterpret_cast<const f32x4*>(a.bias + co);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const int q = q0 + wrow + f * 16 + l15;
-      if (q >= a.nq) continue;
-      const long orow = (long)q * a.ostride + phase + a.ooff;
-      if (orow < 0 || orow >= a.T_out) continue;
-      f32x4 v = acc[g][f] + b;
-      if (res) {
-        const h16x4 rv = *reinterpret_cast<const h16x4*>(res + orow * a.ldres + co);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += (float)rv[e];
-      }
-      if (a.out_act) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a.out_slope;
-      }
-      h16* yp = y + orow * a.ldy + co;
-      if (a.acc != MMS_VOC_ACC_NONE) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= a.scale;
-        if (a.acc == MMS_VOC_ACC_ADD) {
-          const h16x4 pv = *reinterpret_cast<const h16x4*>(yp);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)pv[e];
-        }
-      }
-      h16x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (h16)v[e];
-      *reinterpret_cast<h16x4*>(yp) = o;
-    }
-  }
+__global__ void __launch_bounds__(CT_THREADS) conv1d_tm_kernel(const mms2ut_conv1d_tm_args a) {
+  __shared__ __attribute__((aligned(16))) h16 xs[(conv_tile_positions(SPLITK) + VC_HALO) * CT_LD];
+  __shared__ f32x4 red[conv_red_elems(SPLITK)];
+  conv1d_tm_tile<SPLITK>(VocConvView(a, blockIdx.z), a.Cin, a.Cout, a.taps, xs, red);
 }
 
 int conv_launch(const mms2ut_conv1d_tm_args& a, const char* what, hipStream_t s) {
-  MMS_REQUIRE(a.Cin >= 8 && a.Cin % 8 == 0 && a.Cout >= 8 && a.Cout % 8 == 0,
-              "%s: channel widths must be multiples of 8 and >= 8 (Cin %d, Cout %d)", what, a.Cin, a.Cout);
+  if (int rc = conv_check(what, "", a.Cin, a.Cout, a.x, a.ldx, a.Cin, a.w, a.bias, a.y, a.ldy, a.res, a.ldres, a.Cout))
+    return rc;
   MMS_REQUIRE(a.taps >= 1 && a.dil >= 1 && (long)(a.taps - 1) * a.dil <= VC_HALO,
               "%s: (taps - 1) * dilation must be in [0, %d] (taps %d, dilation %d)", what, VC_HALO, a.taps, a.dil);
   MMS_REQUIRE(a.T_in >= 1 && a.T_out >= 1 && a.nq >= 1 && a.phases >= 1 && a.ostride >= 1, "%s: empty problem", what);
-  MMS_REQUIRE(a.x && a.w && a.y, "%s: null buffer", what);
-  MMS_REQUIRE(a.ldx >= a.Cin && a.ldx % 8 == 0 && a.ldy >= a.Cout && a.ldy % 4 == 0 &&
-                  (!a.res || (a.ldres >= a.Cout && a.ldres % 4 == 0)),
-              "%s: row strides must cover the width and keep rows 16-byte (x) / 8-byte (y, res) aligned", what);
-  MMS_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0 && ((uintptr_t)a.y & 7) == 0 &&
-                  ((uintptr_t)a.res & 7) == 0 && ((uintptr_t)a.bias & 15) == 0, "%s: misaligned buffer", what);
   MMS_REQUIRE(a.acc >= MMS_VOC_ACC_NONE && a.acc <= MMS_VOC_ACC_ADD, "%s: acc mode %d", what, a.acc);
-  const int cy = (a.Cout + VC_TN - 1) / VC_TN;
-  MMS_REQUIRE(a.phases <= 65535 && cy <= 65535, "%s: grid too large", what);
-  // Fewer blocks than CUs and a long reduction: the K-steps' weight loads are a serial latency chain
-  // per wave, so the waves of a block share it out (and the blocks shrink to 32 positions, four times
-  // as many).  With more blocks the short tile loses: it stages up to 96 rows for 32 outputs.
-  // The choice depends on the problem's shape alone, so a shape always takes the same path.
-  long steps = 0;
-  for (int c0 = 0; c0 < a.Cin; c0 += VC_CHUNK) steps += ((long)a.taps * min(VC_CHUNK, a.Cin - c0) + 31) / 32;
-  const long blocks128 = (long)((a.nq + 127) / 128) * cy * a.phases;
-  if (steps >= VC_SPLIT_MIN_STEPS && blocks128 < VC_SPLIT_MAX_BLOCKS) {
-    hipLaunchKernelGGL(conv1d_tm_kernel<true>, dim3((a.nq + 31) / 32, cy, a.phases), dim3(VC_THREADS), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(conv1d_tm_kernel<false>, dim3((a.nq + 127) / 128, cy, a.phases), dim3(VC_THREADS), 0, s, a);
-  }
+  MMS_REQUIRE(a.phases <= 65535, "%s: grid too large", what);
+  conv_tm_launch(conv1d_tm_kernel<true>, conv1d_tm_kernel<false>, a, a.Cin, a.Cout, a.taps, a.nq, a.phases, s);
   return mms::check_launch(what);
 }
 
@@ -356,9 +235,7 @@ extern "C" int mms2ut_conv1d_tm_packed_halves(int Cin, int Cout, int taps, int64
   MMS_REQUIRE(out && Cin >= 8 && Cin % 8 == 0 && Cout >= 8 && Cout % 8 == 0 && taps >= 1,
               "conv1d_tm_packed_halves: channel widths must be multiples of 8 and >= 8 (Cin %d, Cout %d), taps >= 1",
               Cin, Cout);
-  int64_t steps = 0;
-  for (int c0 = 0; c0 < Cin; c0 += VC_CHUNK) steps += ((int64_t)taps * min(VC_CHUNK, Cin - c0) + 31) / 32;
-  *out = steps * ((Cout + 15) & ~15) * 32;
+  *out = conv_ksteps(Cin, taps) * ((Cout + 15) & ~15) * 32;
   return 0;
 }
 

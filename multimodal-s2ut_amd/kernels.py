@@ -1513,38 +1513,59 @@ def _rows16(t, name):
         raise ValueError(f"{name}: time-major [T, C] rows expected, got {tuple(t.shape)} strides {t.stride()}")
 
 
+def _f32c(t, name, n=None):
+    _chk(t, torch.float32)
+    if not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f"{name}: contiguous fp32 tensor of {n} elements expected, got {tuple(t.shape)}")
+
+
+def _conv_tm_io(name, x, w_packed, t_out, Cout, taps, out, bias, res, images=1, groups=1):
+    """What conv1d_tm, conv_transpose1d_tm and asr_conv check alike: x and the packed weight (`images` x
+    `groups` images of Cin / groups -> Cout / groups channels and `taps` taps), out (allocated when None),
+    bias and res.  t_out(T) gives the output length or raises.
+    -> (T, Cin per group, T_out, out, elements of one weight image: 0 where the widths leave it undefined)."""
+    _chk(x)
+    _chk(w_packed)
+    _rows16(x, f"{name} x")
+    T, Cin_all = x.shape
+    if groups < 1 or Cin_all % groups or Cout % groups:
+        raise ValueError(f"{name}: {groups} groups do not divide the widths {Cin_all} -> {Cout}")
+    Cin, Cog = Cin_all // groups, Cout // groups
+    T_out = t_out(T)
+    per = 0
+    if Cin % 8 == 0 and Cin >= 8 and Cog % 8 == 0 and Cog >= 8:      # other widths: the library's message
+        per = conv1d_tm_packed_halves(Cin, Cog, taps)
+        if not w_packed.is_contiguous() or w_packed.numel() != images * groups * per:
+            raise ValueError(f"{name}: packed weight of {w_packed.numel()} elements for {images * groups} x "
+                             f"(Cin {Cin}, Cout {Cog}, taps {taps})")
+    if out is None:
+        out = torch.empty(T_out, Cout, dtype=F16, device=x.device)
+    for t, what in ((out, "out"), (res, "res")):
+        if t is not None:
+            _chk(t)
+            _rows16(t, f"{name} {what}")
+            if tuple(t.shape) != (T_out, Cout):
+                raise ValueError(f"{name}: {what} {tuple(t.shape)}, expected {(T_out, Cout)}")
+    if bias is not None:
+        _f32c(bias, f"{name} bias", Cout)
+    return T, Cin, T_out, out, per
+
+
 def conv1d_tm(x, w_packed, bias, Cout, taps, dil=1, pad=None, *, in_slope=None, res=None, out_slope=None,
               acc=_lib.VOC_ACC_NONE, scale=1.0, out=None):
     """Implicit-GEMM Conv1d over time-major fp16 rows: x [T, Cin] -> [T + 2 pad - dil (taps - 1), Cout].
     in_slope / out_slope: leaky-ReLU on the input as it is read / on the result; res: + res[t] before the
     output activation; acc SET / ADD: out = scale * v / out += scale * v (out required for ADD)."""
-    _chk(x)
-    _chk(w_packed)
-    _rows16(x, "conv1d_tm x")
-    T, Cin = x.shape
     pad = dil * (taps - 1) // 2 if pad is None else pad
-    T_out = T + 2 * pad - dil * (taps - 1)
-    if T_out < 1:
-        raise ValueError(f"conv1d_tm: empty output (T {T}, taps {taps}, dilation {dil}, pad {pad})")
-    if Cin % 8 == 0 and Cin >= 8 and Cout % 8 == 0 and Cout >= 8 and \
-            w_packed.numel() != conv1d_tm_packed_halves(Cin, Cout, taps):
-        raise ValueError(f"conv1d_tm: packed weight of {w_packed.numel()} elements for Cin {Cin}, Cout {Cout}, taps {taps}")
-    if out is None:
-        if acc == _lib.VOC_ACC_ADD:
-            raise ValueError("conv1d_tm: acc ADD needs the tensor to add into")
-        out = torch.empty(T_out, Cout, dtype=F16, device=x.device)
-    _chk(out)
-    _rows16(out, "conv1d_tm out")
-    if tuple(out.shape) != (T_out, Cout):
-        raise ValueError(f"conv1d_tm: out {tuple(out.shape)}, expected {(T_out, Cout)}")
-    if bias is not None:
-        _chk(bias, torch.float32)
-        assert bias.numel() == Cout and bias.is_contiguous()
-    if res is not None:
-        _chk(res)
-        _rows16(res, "conv1d_tm res")
-        if tuple(res.shape) != (T_out, Cout):
-            raise ValueError(f"conv1d_tm: res {tuple(res.shape)}, expected {(T_out, Cout)}")
+
+    def t_out(T):
+        if T + 2 * pad - dil * (taps - 1) < 1:
+            raise ValueError(f"conv1d_tm: empty output (T {T}, taps {taps}, dilation {dil}, pad {pad})")
+        return T + 2 * pad - dil * (taps - 1)
+
+    if out is None and acc == _lib.VOC_ACC_ADD:
+        raise ValueError("conv1d_tm: acc ADD needs the tensor to add into")
+    T, Cin, T_out, out, _ = _conv_tm_io("conv1d_tm", x, w_packed, t_out, Cout, taps, out, bias, res)
     call("mms2ut_conv1d_tm", _lib.CONV1D_TM_ARGS.pack(
         x.data_ptr(), x.stride(0), T, Cin, w_packed.data_ptr(), 0, _p(bias) or 0, out.data_ptr(), out.stride(0),
         T_out, Cout, taps, dil, pad, T_out, 1, 1, 0, int(in_slope is not None), float(in_slope or 0.0),
@@ -1556,27 +1577,13 @@ def conv1d_tm(x, w_packed, bias, Cout, taps, dil=1, pad=None, *, in_slope=None, 
 def conv_transpose1d_tm(x, w_packed, bias, Cout, k, stride, padding, *, in_slope=None, out=None):
     """ConvTranspose1d over time-major fp16 rows as `stride` polyphase convolutions in one launch:
     x [T, Cin] -> [(T - 1) stride - 2 padding + k, Cout]; w_packed from vocoder.pack_conv_transpose_weight."""
-    _chk(x)
-    _chk(w_packed)
-    _rows16(x, "conv_transpose1d_tm x")
-    T, Cin = x.shape
-    T_out = (T - 1) * stride - 2 * padding + k
-    if T_out < 1:
-        raise ValueError(f"conv_transpose1d_tm: empty output (T {T}, k {k}, stride {stride}, padding {padding})")
-    taps = -(-k // stride)
-    if Cin % 8 == 0 and Cin >= 8 and Cout % 8 == 0 and Cout >= 8 and \
-            w_packed.numel() != stride * conv1d_tm_packed_halves(Cin, Cout, taps):
-        raise ValueError(f"conv_transpose1d_tm: packed weight of {w_packed.numel()} elements for Cin {Cin}, "
-                         f"Cout {Cout}, k {k}, stride {stride}")
-    if out is None:
-        out = torch.empty(T_out, Cout, dtype=F16, device=x.device)
-    _chk(out)
-    _rows16(out, "conv_transpose1d_tm out")
-    if tuple(out.shape) != (T_out, Cout):
-        raise ValueError(f"conv_transpose1d_tm: out {tuple(out.shape)}, expected {(T_out, Cout)}")
-    if bias is not None:
-        _chk(bias, torch.float32)
-        assert bias.numel() == Cout and bias.is_contiguous()
+    def t_out(T):
+        if (T - 1) * stride - 2 * padding + k < 1:
+            raise ValueError(f"conv_transpose1d_tm: empty output (T {T}, k {k}, stride {stride}, padding {padding})")
+        return (T - 1) * stride - 2 * padding + k
+
+    T, Cin, _, out, _ = _conv_tm_io("conv_transpose1d_tm", x, w_packed, t_out, Cout, -(-k // stride), out, bias, None,
+                                    images=stride)
     call("mms2ut_conv_transpose1d_tm", x.data_ptr(), x.stride(0), T, Cin, w_packed.data_ptr(), _p(bias),
          out.data_ptr(), out.stride(0), Cout, k, stride, padding, int(in_slope is not None), float(in_slope or 0.0),
          _s())
@@ -1646,12 +1653,6 @@ def var_pred_layer(x, w, b, ln_g, ln_b, *, idx=None, proj=None, eps=1e-5):
 
 # ============================================================================ wav2vec2 CTC transcription
 
-def _f32c(t, name, n=None):
-    _chk(t, torch.float32)
-    if not t.is_contiguous() or (n is not None and t.numel() != n):
-        raise ValueError(f"{name}: contiguous fp32 tensor of {n} elements expected, got {tuple(t.shape)}")
-
-
 def wave_stats(x, eps=1e-7):
     """fp32 [2] = (mean, 1 / sqrt(var + eps)) of the fp32 waveform x [n] (population variance)."""
     _f32c(x, "wave_stats x")
@@ -1690,44 +1691,23 @@ def asr_conv(x, w_packed, bias, Cout, taps, stride=1, pad=0, groups=1, *, T_out=
     gelu (without res): out = GELU(conv + bias), rounded once."""
     if gelu and res is not None:
         raise ValueError("asr_conv: gelu selects the epilogue without a residual; with res the GELU is implied")
-    _chk(x)
-    _chk(w_packed)
-    _rows16(x, "asr_conv x")
-    T, Cin_all = x.shape
-    if groups < 1 or Cin_all % groups or Cout % groups:
-        raise ValueError(f"asr_conv: {groups} groups do not divide the widths {Cin_all} -> {Cout}")
-    Cin, Cog = Cin_all // groups, Cout // groups
-    full = (T + 2 * pad - taps) // stride + 1
-    T_out = full if T_out is None else int(T_out)
-    if T_out < 1 or T_out > full:
-        raise ValueError(f"asr_conv: {T_out} outputs from T {T}, taps {taps}, stride {stride}, pad {pad} (at most {full})")
-    per = 0
-    if Cin % 8 == 0 and Cin >= 8 and Cog % 8 == 0 and Cog >= 8:
-        per = conv1d_tm_packed_halves(Cin, Cog, taps)
-        if not w_packed.is_contiguous() or w_packed.numel() != groups * per:
-            raise ValueError(f"asr_conv: packed weight of {w_packed.numel()} elements for {groups} x (Cin {Cin}, "
-                             f"Cout {Cog}, taps {taps})")
-    if out is None:
-        out = torch.empty(T_out, Cout, dtype=F16, device=x.device)
-    _chk(out)
-    _rows16(out, "asr_conv out")
-    if tuple(out.shape) != (T_out, Cout):
-        raise ValueError(f"asr_conv: out {tuple(out.shape)}, expected {(T_out, Cout)}")
+
+    def t_out(T):
+        full = (T + 2 * pad - taps) // stride + 1
+        n = full if T_out is None else int(T_out)
+        if n < 1 or n > full:
+            raise ValueError(f"asr_conv: {n} outputs from T {T}, taps {taps}, stride {stride}, pad {pad} (at most {full})")
+        return n
+
+    T, Cin, n_out, out, per = _conv_tm_io("asr_conv", x, w_packed, t_out, Cout, taps, out, bias, res, groups=groups)
     # a block stages input rows whose outputs belong to its neighbours: out must not overlap x (res may be x)
     x0, o0 = x.data_ptr(), out.data_ptr()
-    x1, o1 = x0 + ((T - 1) * x.stride(0) + Cin_all) * 2, o0 + ((T_out - 1) * out.stride(0) + Cout) * 2
+    x1, o1 = x0 + ((T - 1) * x.stride(0) + x.shape[1]) * 2, o0 + ((n_out - 1) * out.stride(0) + Cout) * 2
     if x0 < o1 and o0 < x1:
         raise ValueError("asr_conv: out overlaps x; the convolution cannot run in place")
-    if bias is not None:
-        _f32c(bias, "asr_conv bias", Cout)
-    if res is not None:
-        _chk(res)
-        _rows16(res, "asr_conv res")
-        if tuple(res.shape) != (T_out, Cout):
-            raise ValueError(f"asr_conv: res {tuple(res.shape)}, expected {(T_out, Cout)}")
     call("mms2ut_asr_conv", _lib.ASR_CONV_ARGS.pack(
         x.data_ptr(), x.stride(0), T, Cin, w_packed.data_ptr(), per, _p(bias) or 0, out.data_ptr(), out.stride(0),
-        T_out, Cog, int(taps), int(stride), int(pad), int(groups), _p(res) or 0,
+        n_out, Cout // groups, int(taps), int(stride), int(pad), int(groups), _p(res) or 0,
         res.stride(0) if res is not None else 0, 1 if gelu else 0), _s())
     return out
 

@@ -11,8 +11,9 @@ logits, so the order of the top two cannot flip); tests/test_asr.py bounds the s
 asr_conv's block owns 128 output positions, or 32 where its waves split the reduction (at least 4 K-steps
 and fewer than 256 blocks of 128, the vocoder's rule), and 64 output channels; the input channels pass
 through LDS in slices of 64.  Short utterances and the small config only ever reach the 32-position
-kernel, so the kernel tests name the variant each shape takes (_splits restates the rule) and hold shapes
-on both sides of it: at the real width the 128-position kernel runs layer 1 from about 2.6 s of audio."""
+kernel, so the kernel tests name the variant each shape takes (conv_dispatch.splits restates the rule) and
+hold shapes on both sides of it: at the real width the 128-position kernel runs layer 1 from about 2.6 s of
+audio."""
 import importlib.util
 import os
 
@@ -22,6 +23,7 @@ import torch
 
 import asr_ref as AR
 from conftest import ROOT, pkg
+from conv_dispatch import splits as _splits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -75,13 +77,6 @@ def _model(A, cfg_name, seed, blank_bias=0.0):
 
 
 # ------------------------------------------------------------------------------------------ kernels
-
-def _splits(T_out, Cin, Cout, k, groups=1):
-    """asr_conv's dispatch rule restated (csrc/asr.hip mms2ut_asr_conv): True = the 32-position kernel whose
-    waves split K, False = the 128-position kernel.  Cin, Cout per group."""
-    steps = sum(-(-k * min(64, Cin - c0) // 32) for c0 in range(0, Cin, 64))
-    return steps >= 4 and -(-T_out // 128) * -(-Cout // 64) * groups < 256
-
 
 @pytest.mark.parametrize("T,Cin,Cout,k,s,split", [
     (37, 64, 64, 3, 2, True),        # odd T: the trailing row is unused

@@ -18,6 +18,7 @@ import torch
 import asr_ref as AR
 import hubert_ref as HR
 from conftest import ROOT, pkg
+from conv_dispatch import splits as _splits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -57,13 +58,6 @@ def _check(name, got, ref, emu):
     assert torch.isfinite(got).all()
     assert floor > 0 and err <= HR.TOL_FACTOR * floor, (name, err, floor)
     return HR.TOL_FACTOR * floor
-
-
-def _splits(T_out, Cin, Cout, k, groups=1):
-    """asr_conv's dispatch rule restated (csrc/asr.hip mms2ut_asr_conv): True = the 32-position kernel whose
-    waves split K, False = the 128-position kernel.  Cin, Cout per group."""
-    steps = sum(-(-k * min(64, Cin - c0) // 32) for c0 in range(0, Cin, 64))
-    return steps >= 4 and -(-T_out // 128) * -(-Cout // 64) * groups < 256
 
 
 # ------------------------------------------------------------------------------------------ layer 0

@@ -6,7 +6,7 @@ restatement (max-abs) as the restatement's own fp16-storage emulation is for the
 duration predictor is fp32 on the GPU, so its durations are compared for equality.
 
 conv1d_tm's block owns 128 output positions, or 32 where its waves split the reduction (at least
-4 K-steps of 32 and fewer than 256 blocks of 128: csrc/vocoder.hip conv_launch), so the lengths
+4 K-steps of 32 and fewer than 256 blocks of 128: csrc/conv1d_tm.h conv_splits), so the lengths
 "just past one and two tiles" are 129 and 257, and 33 for the short tile; 1 and 7 are shorter than the
 largest halo, d (k - 1) / 2 = 25.  Of CONV_SHAPES, 16->16 k3 and 8->8 k3 (2 and 1 K-steps) take the
 128-position kernel and the others the 32-position one; test_conv1d_tm_block_count_threshold
@@ -16,6 +16,7 @@ import torch
 
 import vocoder_ref as VR
 from conftest import pkg
+from conv_dispatch import splits as _splits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -138,6 +139,24 @@ def test_conv1d_tm_rejects_widths(V, K, Cin, Cout):
     w = torch.zeros(4096, dtype=torch.float16, device=DEV)
     with pytest.raises(L.HipError, match="multiples of 8"):
         K.conv1d_tm(x, w, None, Cout, 3)
+
+
+@pytest.mark.parametrize("T,Cin,Cout,split", [
+    (33, 64, 64, True),              # 6 K-steps: the 32-position kernel, a ragged second block
+    (129, 16, 16, False),            # 2 K-steps: the 128-position kernel, a ragged second block
+    (40, 128, 72, True)])            # 12 K-steps over two Cin slices; Cout off the 64-grid
+def test_asr_conv_and_conv1d_tm_are_one_tile(V, K, T, Cin, Cout, split):
+    """asr_conv at stride 1 and conv1d_tm at dilation 1 are the same convolution through the same tile
+    (csrc/conv1d_tm.h): the same reduction in the same order and one rounding of acc + bias, so the two
+    entry points agree bit for bit."""
+    assert _splits(T, Cin, Cout, 3) == split
+    g = _gen(T + Cin)
+    x = torch.randn(T, Cin, generator=g).half().to(DEV)
+    w = V.pack_conv_weight(torch.randn(Cout, Cin, 3, generator=g) / (Cin * 3) ** 0.5).to(DEV)
+    b = (0.1 * torch.randn(Cout, generator=g)).to(DEV)
+    a, v = K.asr_conv(x, w, b, Cout, 3, stride=1, pad=1), K.conv1d_tm(x, w, b, Cout, 3)
+    assert tuple(a.shape) == tuple(v.shape) == (T, Cout) and bool(v.abs().max() > 0)
+    assert torch.equal(a, v)
 
 
 # ------------------------------------------------------------------------------------------ conv_transpose1d_tm
