@@ -625,6 +625,33 @@ int mms2ut_noise_mix_f32(float* wave, const int64_t* wave_off, int B,
                          const int16_t* bank, const int64_t* bank_off, int n_clips,
                          const int32_t* params, int n_mix, double* ws, hipStream_t stream);
 
+/* ---------------------------------------------------------------- sample-rate conversion
+ * Data preparation (the reference's scripts/preprocess/1_preprocess.ipynb, `ffmpeg -ar 16000`):
+ * bandlimited sinc interpolation in the polyphase form of torchaudio.functional.resample.  With
+ * o = orig / gcd(orig, new), n = new / gcd, K = 2 width + o taps per phase,
+ *   y[j n + i] = sum_{c < K} h[i][c] xp[j o + c],  xp[t] = x[t - width] inside the clip, 0 outside.
+ * x: B mono fp32 clips back to back, in_off[B + 1]; clip b of L samples writes ceil(n L / o)
+ * outputs at y + out_off[b] (and never more than out_off[b + 1] - out_off[b]); max_out: the
+ * longest clip's output count (sizes the grid).  taps: the table tap-major, [K][n] fp32
+ * (taps[c n + i] = h[i][c], built on the host in fp64: prepare.resample_taps), K n at most
+ * MMS_RESAMPLE_MAX_TAPS (4 MiB, an XCD's L2).  y16 (may be null): the same launch also writes
+ * int16 = clip(rint(y), -32768, 32767), manifest.write_wav's rounding, at the same offsets.
+ * Taps outside a clip contribute exactly 0 and a neighbouring clip is never read; an output is
+ * one chain of K fp32 FMAs in tap order, so a clip's result is bit-identical alone, anywhere in
+ * a batch and from run to run.  mms2ut_resample_plan: the output frames (n outputs each) one
+ * block owns for this filter, about MMS_RESAMPLE_TILE outputs, fewer where the input window
+ * ((frames - 1) o + K floats) would exceed MMS_RESAMPLE_LDS_FLOATS; an error where the table is
+ * over the cap or not even MMS_RESAMPLE_R frames fit.                                          */
+#define MMS_RESAMPLE_THREADS    256
+#define MMS_RESAMPLE_R          4
+#define MMS_RESAMPLE_TILE       2048
+#define MMS_RESAMPLE_LDS_FLOATS 16384
+#define MMS_RESAMPLE_MAX_TAPS   (1 << 20)
+int mms2ut_resample_plan(int o, int n, int K, int* tile_frames);
+int mms2ut_resample_f32(const float* x, const int64_t* in_off, const int64_t* out_off, int B,
+                        int64_t max_out, const float* taps, int o, int n, int width, int K, float* y,
+                        int16_t* y16, hipStream_t stream);
+
 /* ---------------------------------------------------------------- unit vocoder (CodeHiFiGAN)
  * Forward-only kernels of fairseq's CodeHiFiGAN generator (csrc/vocoder.hip, vocoder.py).
  * Activations are time-major fp16 rows [T, C]; C is a multiple of 8 and >= 8 everywhere (16-byte

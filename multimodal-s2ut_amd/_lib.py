@@ -304,6 +304,8 @@ SIGNATURES = {
     "mms2ut_fbank_cmvn_collate": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "mms2ut_specaugment_f16": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, vp]),
     "mms2ut_noise_mix_f32": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]),
+    "mms2ut_resample_plan": (i32, [i32, i32, i32, C.POINTER(C.c_int)]),
+    "mms2ut_resample_f32": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp]),
     "mms2ut_conv1d_tm_packed_halves": (i32, [i32, i32, i32, C.POINTER(C.c_int64)]),
     "mms2ut_conv1d_tm": (i32, [vp, vp]),   # CONV1D_TM_ARGS.pack(...) bytes
     "mms2ut_conv_transpose1d_tm": (i32, [vp, i64, i32, i32, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp]),

@@ -1364,6 +1364,53 @@ def noise_mix(wb, bank, bank_off, params, n_mix):
     return wave
 
 
+RESAMPLE_TILE, RESAMPLE_MAX_TAPS = 2048, 1 << 20   # include/mms2ut.h MMS_RESAMPLE_TILE, MMS_RESAMPLE_MAX_TAPS
+
+
+def resample_tile(o, n, K):
+    """Outputs one block of mms2ut_resample_f32 owns for this filter: whole frames of n outputs, about
+    RESAMPLE_TILE of them, fewer where the input window would not fit in LDS (include/mms2ut.h
+    mms2ut_resample_plan).  Raises for a table over RESAMPLE_MAX_TAPS.  Needs no device."""
+    f = _lib.C.c_int(0)
+    call("mms2ut_resample_plan", int(o), int(n), int(K), _lib.C.byref(f))
+    return f.value * int(n)
+
+
+def resample(x, in_off, taps, o, n, width, int16=False):
+    """Polyphase sinc resampling (include/mms2ut.h mms2ut_resample_f32) of mono fp32 clips laid back to
+    back in x; in_off: int64 [B + 1] sample offsets on the host (numpy or CPU tensor), every clip
+    non-empty; taps: fp32 [K, n] on x's device, tap-major (prepare.resample_taps(...)[0].T).
+    -> (y fp32 [total], out_off int64 numpy [B + 1], y16 int16 [total] or None); clip b of L samples owns
+    y[out_off[b]:out_off[b + 1]], ceil(n L / o) samples."""
+    import numpy as np
+    in_off = np.asarray(in_off, dtype=np.int64).reshape(-1)
+    o, n, width = int(o), int(n), int(width)
+    K = 2 * width + o
+    if o < 1 or n < 1 or width < 0 or math.gcd(o, n) != 1:
+        raise ValueError(f"resample: o {o}, n {n} must be coprime and >= 1, width {width} >= 0")
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"resample: contiguous 1-D fp32 device samples expected, got {tuple(x.shape)} {x.dtype}")
+    if taps.shape != (K, n) or taps.dtype != torch.float32 or taps.device != x.device or not taps.is_contiguous():
+        raise ValueError(f"resample: taps {tuple(taps.shape)} {taps.dtype} for K={K}, n={n} (tap-major fp32 on "
+                         f"{x.device} expected)")
+    if in_off.size < 1 or in_off[0] != 0 or in_off[-1] != x.numel():
+        raise ValueError(f"resample: in_off must run from 0 to {x.numel()} samples")
+    lens = np.diff(in_off)
+    if (lens <= 0).any():
+        raise ValueError("resample: empty clip")
+    resample_tile(o, n, K)                      # the table cap and the LDS window, before anything is allocated
+    out_lens = (lens * n + o - 1) // o
+    out_off = np.concatenate([[0], np.cumsum(out_lens)]).astype(np.int64)
+    B, total = int(lens.size), int(out_off[-1])
+    y = torch.empty(total, dtype=torch.float32, device=x.device)
+    y16 = torch.empty(total, dtype=torch.int16, device=x.device) if int16 else None
+    if B:
+        offs = torch.from_numpy(np.stack([in_off, out_off])).to(x.device)
+        call("mms2ut_resample_f32", x.data_ptr(), offs[0].data_ptr(), offs[1].data_ptr(), B, int(out_lens.max()),
+             taps.data_ptr(), o, n, width, K, y.data_ptr(), _p(y16), _s())
+    return y, out_off, y16
+
+
 def log_softmax_step(logits, V, pad, eos, mode=0, out=None):
     """fp32 [rows, V] = log_softmax(logits[:, :V].float()) with the beam-search step masks
     (mode 0: pad; 1: force eos; 2: forbid eos)."""
