@@ -511,6 +511,36 @@ int mms2ut_adam_fp16_master(mms2ut_half* param, const mms2ut_half* grad, float* 
  * lprobs [rows][V] fp32.                                                                    */
 int mms2ut_log_softmax_step(const mms2ut_half* logits, int64_t ld, int64_t rows, int V, int pad_idx,
                             int eos_idx, int mode, float* lprobs, hipStream_t stream);
+/* The same step with fairseq-generate's --temperature and --unkpen: the logit is
+ * fp16(float(logits) / temperature) (fairseq divides the decoder output in its own dtype before the
+ * float cast), and unk_penalty is subtracted from lprobs[:, unk_idx] after the pad mask and before
+ * the eos masks.  temperature > 0.  temperature == 1 and unk_penalty == 0 run
+ * mms2ut_log_softmax_step's kernel: nothing is rounded twice.                                  */
+int mms2ut_log_softmax_step_ext(const mms2ut_half* logits, int64_t ld, int64_t rows, int V, int pad_idx,
+                                int eos_idx, int unk_idx, int mode, float temperature, float unk_penalty,
+                                float* lprobs, hipStream_t stream);
+/* --no-repeat-ngram-size n (fairseq NGramRepeatBlock), one launch per step: for every row r of
+ * tokens [rows][ldt] int64 (history h[0..step], position 0 is </s>) and every start i in
+ * [0, step+1-n] with h[i .. i+n-2] == h[step+2-n .. step], lprobs[r][h[i+n-1]] = -inf; nothing
+ * else is written, and nothing at all while step + 1 < n.  lprobs [rows][V] fp32.  It runs after
+ * the eos masks, so it may ban </s> at a forced-eos step, and n = 1 bans every token of the
+ * history including position 0's </s>.  1 <= n <= 64, step < ldt.                              */
+int mms2ut_ngram_block(const int64_t* tokens, int64_t ldt, int64_t rows, int step, int n, float* lprobs, int V,
+                       hipStream_t stream);
+/* fairseq Sampling.step: draw o = b*beam + slot (b < bsz, slot < beam) samples one token from row
+ * o of lprobs [bsz*beam][V] (from row b*beam when first_step).  Kept set: the whole row in
+ * vocabulary order; with topk > 0 the topk best; with topp > 0 the prefix of the descending order
+ * up to and including the first running sum of expf(lprob) that reaches topp (sorted orders break
+ * ties to the lower index).  With C_j the fp32 running sum over the kept set, the draw is the
+ * smallest j with C_j > u * C_last, u = (h >> 8) * 2^-24, h the 32-bit hash of csrc/common.h
+ * (mms_hash's h) for the counter pair c = ids[b] * 2^32 + step * 2^8 + slot under `seed`.
+ * Outputs [bsz*beam]: out_lprob the row's lprob of the token, out_score = that + prev_scores
+ * [o * ld_prev] (no addend when first_step), out_tok, out_beam = slot, out_kept the kept count.
+ * V <= 4096, beam <= 256; topk and topp exclude each other.                                   */
+int mms2ut_sample_step(const float* lprobs, const float* prev_scores, int64_t ld_prev, const int64_t* ids,
+                       int bsz, int beam, int V, int step, int first_step, uint64_t seed, int topk, float topp,
+                       float* out_score, float* out_lprob, int64_t* out_tok, int64_t* out_beam,
+                       int32_t* out_kept, hipStream_t stream);
 /* One step of decoder self-attention against the K|V cache of one layer,
  * cache [slots][maxT][width = 2*H*hd] (K in columns [0, H*hd), V in [H*hd, 2*H*hd)), addressed
  * through slot [N][maxT] int32: key/value row t (t < T) of hypothesis n is row t of cache slot

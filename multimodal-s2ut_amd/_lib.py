@@ -361,6 +361,9 @@ SIGNATURES = {
     "mms2ut_conv1d_glu_fwd": (i32, [vp, vp, i64, vp]),
     "mms2ut_conv1d_glu_bwd": (i32, [vp, vp, vp, vp, i64, vp, i64, i32, vp, vp]),
     "mms2ut_log_softmax_step": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp]),
+    "mms2ut_log_softmax_step_ext": (i32, [vp, i64, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp]),
+    "mms2ut_ngram_block": (i32, [vp, i64, i64, i32, i32, vp, i32, vp]),
+    "mms2ut_sample_step": (i32, [vp, vp, i64, vp, i32, i32, i32, i32, i32, u64, i32, f32, vp, vp, vp, vp, vp, vp]),
     "mms2ut_kv_cache_gather": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mms2ut_decode_self_attn": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, vp, vp, i64, i64, vp, i64, f32, vp]),
     "mms2ut_decode_embed": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, f32, vp]),

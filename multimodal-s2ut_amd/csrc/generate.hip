@@ -13,31 +13,42 @@
 
 namespace {
 
+// EXT: the step's --temperature and --unkpen.  fairseq divides the decoder output by the temperature
+// in the output's own dtype before the float cast, so the logit is fp16(float(z) / T); the unk
+// penalty is subtracted after the pad mask and before the eos masks (-inf stays -inf).  EXT = false
+// is the T = 1, unkpen = 0 step: no division, no second rounding.
+template <bool EXT>
 __global__ void __launch_bounds__(256) log_softmax_step_kernel(const h16* __restrict__ z, long ld, long rows,
-                                                               int V, int pad, int eos, int mode,
+                                                               int V, int pad, int eos, int mode, int unk,
+                                                               float temperature, float unk_penalty,
                                                                float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const h16* zr = z + row * ld;
+  auto logit = [&](int j) -> float {
+    const float v = (float)zr[j];
+    return EXT ? (float)(h16)(v / temperature) : v;
+  };
   float mx = -INFINITY;
   for (int j = lane; j < V; j += 64) {
-    const float v = (float)zr[j];
+    const float v = logit(j);
     if (v == v) mx = fmaxf(mx, v);
   }
   mx = wave_max(mx);
   float se = 0.f;
   for (int j = lane; j < V; j += 64) {
-    const float v = (float)zr[j];
+    const float v = logit(j);
     if (v == v && v != -INFINITY) se += expf(v - mx);
   }
   se = wave_sum(se);
   const float lse = mx + logf(se);
   float* o = out + row * (long)V;
   for (int j = lane; j < V; j += 64) {
-    const float v = (float)zr[j];
+    const float v = logit(j);
     float r = (v == v) ? v - lse : -INFINITY;
     if (j == pad) r = -INFINITY;
+    if (EXT && j == unk) r -= unk_penalty;
     if (mode == 1 && j != eos) r = -INFINITY;
     if (mode == 2 && j == eos) r = -INFINITY;
     o[j] = r;
@@ -471,7 +482,169 @@ __global__ void __launch_bounds__(256) beam_advance_kernel(const uint8_t* __rest
   }
 }
 
+// --no-repeat-ngram-size n (fairseq NGramRepeatBlock): row r with history h[0..step] may not
+// complete an n-gram it already holds.  s = h[step+2-n .. step] are the last n-1 tokens; every
+// start i in [0, step+1-n] with h[i .. i+n-2] == s bans h[i+n-1].  One block per hypothesis row,
+// threads stride over the starts, the suffix in LDS.  Two matches that ban one token store the same
+// value, so there are no atomics.  Runs after the eos masks, so at a forced-eos step it may ban
+// </s> too, and with n = 1 it bans every token of the history, position 0's </s> included.
+constexpr int NGRAM_MAX = 64;
+
+__global__ void __launch_bounds__(256) ngram_block_kernel(const int64_t* __restrict__ tokens, long ldt, int step,
+                                                          int n, float* __restrict__ lprobs, int V) {
+  __shared__ int64_t s_suf[NGRAM_MAX];
+  const int64_t* h = tokens + (long)blockIdx.x * ldt;
+  const int m = n - 1, s0 = step + 2 - n;      // suffix length and start (s0 >= 0: checked by the host)
+  if ((int)threadIdx.x < m) s_suf[threadIdx.x] = h[s0 + threadIdx.x];
+  __syncthreads();
+  float* lp = lprobs + (long)blockIdx.x * V;
+  for (int i = threadIdx.x; i <= step + 1 - n; i += 256) {
+    bool eq = true;
+    for (int t = 0; t < m && eq; ++t) eq = h[i + t] == s_suf[t];
+    if (eq) {
+      const int64_t tok = h[i + m];
+      if (tok >= 0 && tok < V) lp[tok] = -INFINITY;
+    }
+  }
+}
+
+// fairseq Sampling.step for one draw per block: the kept set is the whole row in vocabulary order,
+// or the K best (top-k) / the shortest sorted prefix whose probability reaches P (top-p), sorted
+// descending with beam_topk's tie rule (a bitonic sort of beam_key(lprob, index) in LDS).  With
+// p_j = expf(lprob_j) in that order and C_j its running sum, the draw is the smallest j with
+// C_j > u * C_last.  C_j = fl(off_t + l_j): l_j the sequential sum inside thread t's contiguous
+// chunk, off_{t+1} = fl(off_t + l_last), so C never decreases and stays put over a p_j = 0 — a
+// token of probability 0 is never the smallest j.  u = (h >> 8) * 2^-24 with h the 32-bit hash
+// that common.h's mms_hash forms for the counter pair c (the hash counters 2c and 2c + 1 share),
+// c = id * 2^32 + step * 2^8 + slot: a function of the sentence's id, not of its batch.
+constexpr int SAMPLE_MAX_V = 4096;
+
+MMS_DEV uint32_t pair_hash(uint64_t seed, uint64_t pair) {
+  const uint32_t s = (uint32_t)seed ^ mms_mix32((uint32_t)(seed >> 32) + 0x9e3779b9U);
+  return mms_mix32((uint32_t)pair ^ mms_mix32((uint32_t)(pair >> 32) ^ s));
+}
+
+MMS_DEV float key_score(uint64_t key) {
+  uint32_t u = (uint32_t)(key >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+  return __uint_as_float(u);
+}
+
+__global__ void __launch_bounds__(256) sample_step_kernel(const float* __restrict__ lprobs,
+                                                          const float* __restrict__ prev, long ld_prev,
+                                                          const int64_t* __restrict__ ids, int beam, int V, int P2,
+                                                          int step, int first_step, uint64_t seed, int topk,
+                                                          float topp, float* __restrict__ out_score,
+                                                          float* __restrict__ out_lprob,
+                                                          int64_t* __restrict__ out_tok,
+                                                          int64_t* __restrict__ out_beam,
+                                                          int* __restrict__ out_kept) {
+  extern __shared__ uint64_t s_key[];                       // [P2] when sorting, else unused
+  const bool sorted = topk > 0 || topp > 0.f;
+  float* s_c = reinterpret_cast<float*>(s_key + (sorted ? P2 : 0));   // [V] p_j, then C_j
+  __shared__ float s_off[257];
+  __shared__ int s_cnt[2];
+  const int tid = threadIdx.x;
+  const long o = blockIdx.x;                                // the draw: sentence b, slot
+  const long b = o / beam;
+  const int slot = (int)(o - b * beam);
+  const long src = first_step ? b * beam : o;               // step 0: every draw from the first row
+  const float* lp = lprobs + src * V;
+  if (tid < 2) s_cnt[tid] = 0;
+  if (sorted) {
+    for (int i = tid; i < P2; i += 256) s_key[i] = i < V ? beam_key(lp[i], (uint32_t)i) : 0ull;
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < P2; i += 256) {
+          const int x = i ^ j;
+          if (x > i) {
+            const uint64_t a = s_key[i], c = s_key[x];
+            if (((i & k) == 0) ? a < c : a > c) { s_key[i] = c; s_key[x] = a; }
+          }
+        }
+        __syncthreads();
+      }
+  }
+  // chunk sums, the 256 offsets in sequence, then the running sums
+  const int per = (V + 255) / 256, j0 = tid * per, j1 = min(V, j0 + per);
+  float l = 0.f;
+  for (int j = j0; j < j1; ++j) {
+    l += expf(sorted ? key_score(s_key[j]) : lp[j]);
+    s_c[j] = l;
+  }
+  s_off[tid + 1] = l;
+  __syncthreads();
+  if (tid == 0) {
+    float off = 0.f;
+    s_off[0] = 0.f;
+    for (int t = 1; t <= 256; ++t) { off += s_off[t]; s_off[t] = off; }
+  }
+  __syncthreads();
+  const float off = s_off[tid];
+  int below = 0;
+  for (int j = j0; j < j1; ++j) {
+    const float c = off + s_c[j];
+    s_c[j] = c;
+    below += c < topp;
+  }
+  if (topp > 0.f && below) atomicAdd(&s_cnt[0], below);
+  __syncthreads();
+  int kept = V;
+  if (topk > 0) kept = min(topk, V);
+  else if (topp > 0.f) kept = min(V, s_cnt[0] + 1);
+  const float total = s_c[kept - 1];
+  const uint64_t ctr = ((uint64_t)ids[b] << 32) + ((uint64_t)step << 8) + (uint64_t)slot;
+  const float thr = (float)(pair_hash(seed, ctr) >> 8) * 5.9604644775390625e-8f * total;
+  int le = 0;
+  for (int j = j0; j < min(j1, kept); ++j) le += s_c[j] <= thr;
+  if (le) atomicAdd(&s_cnt[1], le);
+  __syncthreads();
+  if (tid == 0) {
+    const int j = min(s_cnt[1], kept - 1);
+    const int tok = sorted ? (int)(0xFFFFFFFFu - (uint32_t)s_key[j]) : j;
+    const float v = lp[tok];
+    out_lprob[o] = v;
+    out_score[o] = prev ? v + prev[o * ld_prev] : v;
+    out_tok[o] = tok;
+    out_beam[o] = slot;
+    out_kept[o] = kept;
+  }
+}
+
 }  // namespace
+
+extern "C" int mms2ut_ngram_block(const int64_t* tokens, int64_t ldt, int64_t rows, int step, int n, float* lprobs,
+                                  int V, hipStream_t s) {
+  MMS_REQUIRE(n >= 1 && n <= NGRAM_MAX, "ngram_block: need 1 <= n <= 64");
+  MMS_REQUIRE(step >= 0 && (long)step < ldt, "ngram_block: history rows too short for step (need step < ldt)");
+  MMS_REQUIRE(V > 0 && rows >= 0 && rows < 0x7FFFFFFFL, "ngram_block: need V > 0 and 0 <= rows < 2^31");
+  if (rows == 0 || step + 1 - n < 0) return 0;              // no start position yet: nothing is banned
+  hipLaunchKernelGGL(ngram_block_kernel, dim3((unsigned)rows), dim3(256), 0, s, tokens, (long)ldt, step, n, lprobs,
+                     V);
+  return mms::check_launch("ngram_block");
+}
+
+extern "C" int mms2ut_sample_step(const float* lprobs, const float* prev_scores, int64_t ld_prev,
+                                  const int64_t* ids, int bsz, int beam, int V, int step, int first_step,
+                                  uint64_t seed, int topk, float topp, float* out_score, float* out_lprob,
+                                  int64_t* out_tok, int64_t* out_beam, int32_t* out_kept, hipStream_t s) {
+  MMS_REQUIRE(V >= 1 && V <= SAMPLE_MAX_V, "sample_step: V must be in [1, 4096]");
+  MMS_REQUIRE(beam >= 1 && beam <= 256, "sample_step: beam must be in [1, 256]");
+  MMS_REQUIRE(step >= 0 && step < (1 << 24), "sample_step: step must be in [0, 2^24)");
+  MMS_REQUIRE(!(topk > 0 && topp > 0.f), "sample_step: top-k and top-p exclude each other");
+  MMS_REQUIRE(bsz >= 0 && (long)bsz * beam < 0x7FFFFFFFL, "sample_step: bsz * beam too large");
+  MMS_REQUIRE(ids != nullptr, "sample_step: sentence ids required");
+  if (bsz == 0) return 0;
+  int P2 = 64;
+  while (P2 < V) P2 <<= 1;
+  const bool sorted = topk > 0 || topp > 0.f;
+  const size_t lds = (sorted ? (size_t)P2 * 8 : 0) + (size_t)V * 4;
+  const float* prev = first_step ? nullptr : prev_scores;
+  hipLaunchKernelGGL(sample_step_kernel, dim3(bsz * beam), dim3(256), lds, s, lprobs, prev, (long)ld_prev, ids, beam,
+                     V, P2, step, first_step, seed, topk, topp, out_score, out_lprob, out_tok, out_beam, out_kept);
+  return mms::check_launch("sample_step");
+}
 
 extern "C" int mms2ut_beam_eos_scan(const float* cand_score, const int64_t* cand_tok, const uint8_t* ignore, int bsz,
                                     int beam, int k, int eos_idx, uint8_t* eos_mask, int32_t* count,
@@ -505,9 +678,27 @@ extern "C" int mms2ut_log_softmax_step(const h16* logits, int64_t ld, int64_t ro
   MMS_REQUIRE(ld >= V && V > 0, "log_softmax_step: ld must be >= V > 0");
   MMS_REQUIRE(mode >= 0 && mode <= 2, "log_softmax_step: mode must be 0, 1 or 2");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(log_softmax_step_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, (long)ld,
-                     (long)rows, V, pad_idx, eos_idx, mode, lprobs);
+  hipLaunchKernelGGL(log_softmax_step_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, s, logits, (long)ld,
+                     (long)rows, V, pad_idx, eos_idx, mode, -1, 1.f, 0.f, lprobs);
   return mms::check_launch("log_softmax_step");
+}
+
+extern "C" int mms2ut_log_softmax_step_ext(const h16* logits, int64_t ld, int64_t rows, int V, int pad_idx,
+                                           int eos_idx, int unk_idx, int mode, float temperature,
+                                           float unk_penalty, float* lprobs, hipStream_t s) {
+  MMS_REQUIRE(ld >= V && V > 0, "log_softmax_step_ext: ld must be >= V > 0");
+  MMS_REQUIRE(mode >= 0 && mode <= 2, "log_softmax_step_ext: mode must be 0, 1 or 2");
+  MMS_REQUIRE(temperature > 0.f, "log_softmax_step_ext: temperature must be greater than 0");
+  MMS_REQUIRE(unk_penalty == unk_penalty, "log_softmax_step_ext: unk_penalty is NaN");
+  if (rows == 0) return 0;
+  const dim3 grid((rows + 3) / 4);
+  if (temperature == 1.f && unk_penalty == 0.f)   // today's step, bit for bit
+    hipLaunchKernelGGL(log_softmax_step_kernel<false>, grid, dim3(256), 0, s, logits, (long)ld, (long)rows, V,
+                       pad_idx, eos_idx, mode, -1, 1.f, 0.f, lprobs);
+  else
+    hipLaunchKernelGGL(log_softmax_step_kernel<true>, grid, dim3(256), 0, s, logits, (long)ld, (long)rows, V,
+                       pad_idx, eos_idx, mode, unk_idx, temperature, unk_penalty, lprobs);
+  return mms::check_launch("log_softmax_step_ext");
 }
 
 extern "C" int mms2ut_kv_cache_gather(const h16* src, h16* dst, const int64_t* idx, int L, int Nsrc, int N,

@@ -20,8 +20,9 @@ Two parts:
   logits GEMM, then ``log_softmax_step`` (log_softmax of the fp16 logits in fp32 fused with the
   step's pad / eos masking).
 * ``SequenceGenerator`` — fairseq ``SequenceGenerator._generate`` + ``BeamSearch.step`` +
-  ``finalize_hypos`` (normalize_scores, len_penalty, min_len 1, no unk penalty / n-gram blocking /
-  prefix / constraints), as device tensor bookkeeping around the decoder above: candidate selection
+  ``finalize_hypos`` (normalize_scores, len_penalty, min_len, temperature, unk penalty, n-gram
+  blocking and fairseq's ``Sampling`` search; no prefix / constraints / diverse beam search), as
+  device tensor bookkeeping around the decoder above: candidate selection
   (``beam_topk``) and the per-step bookkeeping (``beam_eos_scan``, ``beam_advance``) are HIP kernels
   when the decoder exposes them, torch (``TorchBookkeeping``) otherwise; finalisation and the removal
   of finished sentences are torch.  Works with any decoder object exposing
@@ -185,7 +186,13 @@ class IncrementalDecoder:
                                             tokens, scores, step, spare[0], spare[1])
         return new_ignore, active, spare[0], spare[1]
 
-    def step(self, tokens_last, step, mode=MODE_NONE):
+    def ngram_block(self, tokens, lprobs, step, n):
+        return K.ngram_block(tokens, lprobs, step, n)
+
+    def sample_step(self, lprobs, prev_col, ids, bsz, beam, V, step, seed, topk=-1, topp=-1.0):
+        return K.sample_step(lprobs, prev_col, ids, bsz, beam, V, step, seed, topk, topp)[:3]
+
+    def step(self, tokens_last, step, mode=MODE_NONE, temperature=1.0, unk_penalty=0.0):
         """tokens_last [N] int64 (the token at position `step` of every hypothesis) -> lprobs [N, V]."""
         assert self.step_no == step and self.slot.shape[0] == self.N and step + 1 < self.maxT
         self.tok.copy_(tokens_last)
@@ -203,7 +210,103 @@ class IncrementalDecoder:
             self._body()
             self.eager_steps += 1
         self.step_no += 1
-        return K.log_softmax_step(self.logits, self.V, self.pad, self.eos, mode)
+        if temperature == 1.0 and unk_penalty == 0.0:
+            return K.log_softmax_step(self.logits, self.V, self.pad, self.eos, mode)
+        return K.log_softmax_step_ext(self.logits, self.V, self.pad, self.eos, mode, temperature, unk_penalty)
+
+
+def normalize_step(logits, pad, eos, mode=MODE_NONE, temperature=1.0, unk_penalty=0.0, unk=K.UNK):
+    """fairseq's per-step normalisation of fp16 decoder logits [N, V] in torch, in its order:
+    logits / temperature in fp16, log_softmax in fp32, NaN -> -inf, pad -> -inf,
+    lprobs[:, unk] -= unk_penalty, then the forced / forbidden eos of ``mode``.  What
+    ``log_softmax_step_ext`` computes on the device, and what a decoder without it (the CPU tests'
+    toy decoder) calls."""
+    z = logits
+    if temperature != 1.0:
+        z = (z.float() / temperature).to(F16)
+    z = z.float()
+    z = torch.where(torch.isnan(z), torch.full_like(z, -math.inf), z)
+    lp = torch.log_softmax(z, -1)
+    lp[:, pad] = -math.inf
+    lp[:, unk] -= unk_penalty
+    if mode == MODE_FORCE_EOS:
+        keep = lp[:, eos].clone()
+        lp[:] = -math.inf
+        lp[:, eos] = keep
+    elif mode == MODE_NO_EOS:
+        lp[:, eos] = -math.inf
+    return lp
+
+
+def torch_ngram_block(tokens, lprobs, step, n):
+    """--no-repeat-ngram-size n in torch, in place on lprobs [N, V] (the reference of
+    ``kernels.ngram_block``): with h = tokens[r, :step + 1], every start i in [0, step + 1 - n]
+    whose n - 1 tokens equal the last n - 1 of h bans h[i + n - 1].  n = 1 bans every token of the
+    history (an empty suffix matches everywhere), position 0's </s> included."""
+    if step + 1 - n < 0:
+        return lprobs
+    h = tokens[:, : step + 1]
+    win = h.unfold(1, n, 1)                               # [N, step + 2 - n, n]: the n-grams of h
+    match = (win[:, :, : n - 1] == h[:, step + 2 - n:].unsqueeze(1)).all(-1)
+    rows, pos = match.nonzero(as_tuple=True)
+    lprobs[rows, win[rows, pos, n - 1]] = -math.inf
+    return lprobs
+
+
+def _mix32(x):
+    """csrc/common.h mms_mix32 on int64 tensors holding 32-bit values."""
+    m = 0xFFFFFFFF
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & m
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & m              # wraps modulo 2^64: the low 32 bits are exact
+    return x ^ (x >> 16)
+
+
+def sample_uniform(seed, ids, step, slots):
+    """The sampling stream: u = (h >> 8) * 2^-24 (float64, exact), h the 32-bit hash csrc/common.h's
+    mms_hash forms for counter pair c = id * 2^32 + step * 2^8 + slot — the hash the counters 2c
+    and 2c + 1 share.  ids, slots: int64 tensors of one shape."""
+    seed &= 0xFFFFFFFFFFFFFFFF
+    s = (seed & 0xFFFFFFFF) ^ int(_mix32(torch.tensor(((seed >> 32) + 0x9E3779B9) & 0xFFFFFFFF)))
+    lo = (step * 256 + slots) & 0xFFFFFFFF
+    hi = (ids + ((step * 256 + slots) >> 32)) & 0xFFFFFFFF
+    h = _mix32(lo ^ _mix32(hi ^ s))
+    return (h >> 8).double() * 2.0 ** -24
+
+
+def torch_sample_step(lprobs, prev_col, ids, bsz, beam, V, step, seed, topk=-1, topp=-1.0):
+    """fairseq Sampling.step in torch with the stream above (the reference of
+    ``kernels.sample_step``; fp32 ``exp`` as there and in fairseq, so an underflowing probability is 0
+    on both paths, then fp64 running sums) -> (scores, tokens, beams) [bsz, beam]."""
+    dev = lprobs.device
+    lp = lprobs.view(bsz, beam, V)
+    if step == 0:
+        lp = lp[:, :1, :].expand(bsz, beam, V)
+    if topk > 0 or topp > 0:
+        # descending, ties to the lower index: a stable sort of the negated scores
+        order = torch.sort(-lp, dim=-1, stable=True)[1]
+        slp = lp.gather(-1, order)
+    else:
+        order, slp = None, lp
+    c = slp.exp().double().cumsum(-1)
+    if topk > 0:
+        kept = torch.full((bsz, beam), min(topk, V), dtype=torch.long, device=dev)
+    elif topp > 0:
+        kept = ((c < topp).sum(-1) + 1).clamp(max=V)
+    else:
+        kept = torch.full((bsz, beam), V, dtype=torch.long, device=dev)
+    total = c.gather(-1, (kept - 1).unsqueeze(-1))
+    slots = torch.arange(beam, device=dev).expand(bsz, beam)
+    u = sample_uniform(seed, ids.view(bsz, 1).expand(bsz, beam), step, slots)
+    j = (c <= (u.unsqueeze(-1) * total)).logical_and(
+        torch.arange(V, device=dev) < kept.unsqueeze(-1)).sum(-1)
+    j = torch.minimum(j, kept - 1)
+    tok = j if order is None else order.gather(-1, j.unsqueeze(-1)).squeeze(-1)
+    sc = lp.gather(-1, tok.unsqueeze(-1)).squeeze(-1)
+    if step > 0:
+        sc = sc + prev_col.view(bsz, beam)
+    return sc.contiguous(), tok.contiguous(), slots.contiguous()
 
 
 class TorchBookkeeping:
@@ -250,7 +353,20 @@ class SequenceGenerator:
     """fairseq SequenceGenerator (beam search) over a step/reorder decoder."""
 
     def __init__(self, beam_size=10, max_len_a=1.0, max_len_b=200, max_len=3000, min_len=1,
-                 normalize_scores=True, len_penalty=1.0, pad=1, eos=2):
+                 normalize_scores=True, len_penalty=1.0, pad=1, eos=2, temperature=1.0, unk_penalty=0.0,
+                 no_repeat_ngram_size=0, sampling=False, sampling_topk=-1, sampling_topp=-1.0, seed=1):
+        if not temperature > 0:
+            raise ValueError(f"--temperature must be greater than 0, got {temperature}")
+        if no_repeat_ngram_size < 0:
+            raise ValueError(f"--no-repeat-ngram-size must be >= 0, got {no_repeat_ngram_size}")
+        if sampling_topk > 0 and sampling_topp > 0:
+            raise ValueError("--sampling-topk and --sampling-topp exclude each other")
+        if (sampling_topk > 0 or sampling_topp > 0) and not sampling:
+            raise ValueError("--sampling-topk / --sampling-topp require --sampling")
+        if sampling and beam_size > K.SAMPLE_MAX_BEAM:
+            raise ValueError(f"--sampling needs --beam <= {K.SAMPLE_MAX_BEAM}, got {beam_size}")
+        self.temperature, self.unk_penalty, self.ngram = temperature, unk_penalty, no_repeat_ngram_size
+        self.sampling, self.topk, self.topp, self.seed = sampling, sampling_topk, sampling_topp, seed
         self.beam = beam_size
         self.max_len_a, self.max_len_b, self.max_len = max_len_a, max_len_b, max_len
         self.min_len, self.normalize_scores, self.len_penalty = min_len, normalize_scores, len_penalty
@@ -260,8 +376,20 @@ class SequenceGenerator:
         """max_len = min(a·src_len + b, max_len - 1) (src_len: padded source frames)."""
         return min(int(self.max_len_a * src_len + self.max_len_b), self.max_len - 1)
 
-    def generate(self, decoder, bsz, max_len, V, device):
+    def generate(self, decoder, bsz, max_len, V, device, sample_ids=None):
+        """sample_ids [bsz] int64: the sentences' ids, the key of the sampling stream (arange(bsz)
+        when None), so that a sentence's samples do not depend on the batch it fell into."""
         beam, pad, eos = self.beam, self.pad, self.eos
+        if self.sampling:
+            sample_ids = torch.arange(bsz, device=device) if sample_ids is None else \
+                torch.as_tensor(sample_ids, dtype=torch.long, device=device).contiguous()
+            if sample_ids.shape != (bsz,):
+                raise ValueError(f"sample_ids must hold {bsz} ids, got shape {tuple(sample_ids.shape)}")
+        # --temperature / --unkpen are the decoder step's (fused with its log-softmax); a default
+        # search calls step() with the three arguments it always had
+        controls = {}
+        if self.temperature != 1.0 or self.unk_penalty != 0.0:
+            controls = {"temperature": self.temperature, "unk_penalty": self.unk_penalty}
         N = bsz * beam
         scores = torch.zeros(N, max_len + 1, dtype=torch.float32, device=device)
         tokens = torch.full((N, max_len + 2), pad, dtype=torch.long, device=device)
@@ -283,10 +411,20 @@ class SequenceGenerator:
                     reorder_state.view(-1, beam).add_(corr.unsqueeze(-1) * beam)
                 decoder.reorder(reorder_state, batch_idxs)
             mode = MODE_FORCE_EOS if step >= max_len else (MODE_NO_EOS if step < self.min_len else MODE_NONE)
-            lprobs = decoder.step(tokens[:, step], step, mode)
-            # BeamSearch.step
-            k = min(cand_size, (1 if step == 0 else beam) * V - 1)
-            if hasattr(decoder, "beam_topk"):     # HIP selection kernel (ties to the lower flat index)
+            lprobs = decoder.step(tokens[:, step], step, mode, **controls)
+            if self.ngram > 0:                    # after the eos masks, as fairseq: may ban a forced </s>
+                if hasattr(decoder, "ngram_block"):
+                    decoder.ngram_block(tokens, lprobs, step, self.ngram)
+                else:
+                    torch_ngram_block(tokens, lprobs, step, self.ngram)
+            # BeamSearch.step, or Sampling.step (candidate width beam, cand_beams = arange(beam))
+            k = beam if self.sampling else min(cand_size, (1 if step == 0 else beam) * V - 1)
+            if self.sampling:
+                draw = decoder.sample_step if hasattr(decoder, "sample_step") else torch_sample_step
+                cand_scores, cand_indices, cand_beams = draw(
+                    lprobs, None if step == 0 else scores[:, step - 1], sample_ids, bsz, beam, V, step, self.seed,
+                    self.topk, self.topp)
+            elif hasattr(decoder, "beam_topk"):   # HIP selection kernel (ties to the lower flat index)
                 cand_scores, cand_indices, cand_beams = decoder.beam_topk(
                     lprobs, None if step == 0 else scores[:, step - 1], bsz, beam, V, k, step == 0)
             else:
@@ -323,6 +461,8 @@ class SequenceGenerator:
                 cand_scores = cand_scores[batch_idxs]
                 cand_indices = cand_indices[batch_idxs]
                 cands_to_ignore = cands_to_ignore[batch_idxs]
+                if self.sampling:
+                    sample_ids = sample_ids[batch_idxs]
                 scores = scores.view(bsz, -1)[batch_idxs].view(new_bsz * beam, -1)
                 tokens = tokens.view(bsz, -1)[batch_idxs].view(new_bsz * beam, -1)
                 bsz = new_bsz
@@ -372,8 +512,11 @@ class SequenceGenerator:
 
 
 def generate(model, batch, beam_size=10, max_len_a=1.0, max_len_b=200, max_len=None, len_penalty=1.0,
-             min_len=1):
-    """fairseq-generate on one DeviceBatch: encoder (eval, fusion included) -> beam search.
+             min_len=1, temperature=1.0, unk_penalty=0.0, no_repeat_ngram_size=0, sampling=False,
+             sampling_topk=-1, sampling_topp=-1.0, seed=1, sample_ids=None):
+    """fairseq-generate on one DeviceBatch: encoder (eval, fusion included) -> beam search, or
+    fairseq's Sampling search with ``sampling`` (``sample_ids`` [bsz]: the sentences' ids that key
+    the sampling stream, arange(bsz) when None).
     Returns, per sentence in batch order, the hypotheses sorted by score (fairseq's dicts)."""
     was = model.training
     model.eval()
@@ -382,9 +525,15 @@ def generate(model, batch, beam_size=10, max_len_a=1.0, max_len_b=200, max_len=N
         bsz = batch.src.shape[0]
         gen = SequenceGenerator(beam_size, max_len_a, max_len_b,
                                 max_len or model.cfg["max_target_positions"], min_len=min_len,
-                                len_penalty=len_penalty, pad=model.cfg["padding_idx"])
+                                len_penalty=len_penalty, pad=model.cfg["padding_idx"], temperature=temperature,
+                                unk_penalty=unk_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                sampling=sampling, sampling_topk=sampling_topk, sampling_topp=sampling_topp,
+                                seed=seed)
+        if sampling and model.cfg["vocab_size"] > K.SAMPLE_MAX_V:
+            raise NotImplementedError(f"--sampling: vocabulary {model.cfg['vocab_size']} exceeds the sampling "
+                                      f"kernel's limit of {K.SAMPLE_MAX_V}")
         T = gen.max_steps(batch.src.shape[1])
         dec = IncrementalDecoder(model, enc, enc_len32, Te, bsz, beam_size, T)
-        return gen.generate(dec, bsz, T, model.cfg["vocab_size"], enc.device)
+        return gen.generate(dec, bsz, T, model.cfg["vocab_size"], enc.device, sample_ids=sample_ids)
     finally:
         model.train(was)

@@ -9,6 +9,10 @@ manifest split in, ``generate-{subset}.txt`` and ``generate-{subset}.unit`` out.
 
 The architecture comes from the checkpoint's saved ``args``; task and data flags not given on the
 command line fall back to the saved ones (``plugins.merge_generate_args``).  One process, one GPU.
+fairseq-generate's search controls are accepted with its defaults: ``--temperature``, ``--unkpen``,
+``--no-repeat-ngram-size``, and ``--sampling`` with ``--sampling-topk`` / ``--sampling-topp`` (a
+replayable stream keyed by ``--seed`` and the sentence's row in the manifest; ``--nbest`` prints the
+sampled hypotheses).
 
 Output lines follow fairseq ``fairseq_cli/generate.py`` (restated from its published source;
 fairseq is not importable here, so the format is not pinned against the library).  Per sentence,
@@ -40,7 +44,7 @@ import time
 
 import torch
 
-from .plugins import REGISTRY, merge_generate_args, parse_generate_args
+from .plugins import REGISTRY, merge_generate_args, parse_generate_args, search_controls
 
 log = logging.getLogger("mms2ut.generate")
 LN2 = math.log(2)
@@ -162,11 +166,16 @@ def main(argv=None):
         cfg = dict(net.cfg, multitask=None)      # the auxiliary heads are not run: no text targets
         torch.cuda.synchronize(dev)
         t0, captures0 = time.perf_counter(), G.graph_captures()
+        controls = search_controls(args)         # the sampling stream is keyed by the manifest index
         for batch, sample in M.DeviceLoader(ds, batches, cfg, dev, seed=getattr(args, "seed", 1) or 1):
             # the search of task.build_generator / inference_step, on the loader's device batch
             hypos = G.generate(net, batch, beam_size=args.beam, max_len_a=args.max_len_a, max_len_b=args.max_len_b,
-                               len_penalty=args.lenpen, min_len=args.min_len)
+                               len_penalty=args.lenpen, min_len=args.min_len,
+                               sample_ids=sample["id"] if args.sampling else None, **controls)
             for i, sid in enumerate(sample["id"].tolist()):
+                if not hypos[i]:             # n-gram blocking banned </s> at every step it could end
+                    raise SystemExit(f"mms2ut-generate: sentence {sid} has no finished hypothesis "
+                                     f"(--no-repeat-ngram-size {args.no_repeat_ngram_size} bans its </s>)")
                 block = format_sentence(sid, ds.tgt_texts[sid], hypos[i], ds.tgt_dict, args.nbest)
                 print("\n".join(block), file=out)
                 lines += block

@@ -1421,6 +1421,77 @@ def log_softmax_step(logits, V, pad, eos, mode=0, out=None):
     return out
 
 
+UNK = 3                    # fairseq Dictionary: <s> 0, <pad> 1, </s> 2, <unk> 3
+SAMPLE_MAX_V = 4096        # sample_step keeps one row's (lprob, index) pairs in LDS
+SAMPLE_MAX_BEAM = 256      # the draw's slot takes 8 bits of the stream's counter
+
+
+def log_softmax_step_ext(logits, V, pad, eos, mode=0, temperature=1.0, unk_penalty=0.0, unk=UNK, out=None):
+    """log_softmax_step with --temperature (logit = fp16(float(z) / T)) and --unkpen (subtracted
+    from column ``unk`` between the pad mask and the eos masks).  T = 1, unkpen = 0 is
+    log_softmax_step bit for bit."""
+    if not temperature > 0:
+        raise ValueError(f"log_softmax_step_ext: temperature must be greater than 0, got {temperature}")
+    if logits.dtype != F16 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < V:
+        raise ValueError(f"log_softmax_step_ext: logits must be fp16 [rows, >= {V}] with unit column stride, got "
+                         f"{logits.dtype} {tuple(logits.shape)}")
+    rows = logits.shape[0]
+    out = torch.empty(rows, V, dtype=torch.float32, device=logits.device) if out is None else out
+    call("mms2ut_log_softmax_step_ext", logits.data_ptr(), logits.stride(0), rows, int(V), int(pad), int(eos),
+         int(unk), int(mode), float(temperature), float(unk_penalty), out.data_ptr(), _s())
+    return out
+
+
+def ngram_block(tokens, lprobs, step, n):
+    """--no-repeat-ngram-size n on lprobs [N, V] fp32 in place (mms2ut_ngram_block): tokens [N, ld]
+    int64 are the histories, columns [0, step] filled.  Returns lprobs."""
+    N, V = lprobs.shape
+    if tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.shape[0] != N or not tokens.is_contiguous() \
+            or lprobs.dtype != torch.float32 or not lprobs.is_contiguous() or tokens.device != lprobs.device:
+        raise ValueError(f"ngram_block: expected contiguous int64 tokens [{N}, ld] and fp32 lprobs [{N}, {V}] on one "
+                         f"device, got {tokens.dtype} {tuple(tokens.shape)} and {lprobs.dtype} {tuple(lprobs.shape)}")
+    if not 0 <= step < tokens.shape[1]:
+        raise ValueError(f"ngram_block: step {step} outside the histories' {tokens.shape[1]} columns")
+    if n < 1 or n > 64:
+        raise ValueError(f"ngram_block: n must be in [1, 64], got {n}")
+    call("mms2ut_ngram_block", tokens.data_ptr(), tokens.shape[1], N, int(step), int(n), lprobs.data_ptr(), V, _s())
+    return lprobs
+
+
+def sample_step(lprobs, prev_col, ids, bsz, beam, V, step, seed, topk=-1, topp=-1.0, first_step=None):
+    """fairseq Sampling.step (mms2ut_sample_step) -> (scores, tokens, beams [bsz, beam], lprob
+    [bsz, beam] f32 the drawn token's own lprob, kept [bsz, beam] i32 the size of the set drawn
+    from).  lprobs [bsz*beam, V] fp32, prev_col a strided fp32 column [bsz*beam] of the cumulative
+    scores (None at the first step), ids int64 [bsz] the sentences' ids (the stream's key)."""
+    first_step = step == 0 if first_step is None else first_step
+    if V > SAMPLE_MAX_V:
+        raise NotImplementedError(f"sample_step: vocabulary {V} exceeds the kernel's limit of {SAMPLE_MAX_V}")
+    if beam > SAMPLE_MAX_BEAM:
+        raise ValueError(f"sample_step: beam {beam} exceeds {SAMPLE_MAX_BEAM}")
+    if topk > 0 and topp > 0:
+        raise ValueError("sample_step: top-k and top-p exclude each other")
+    dev = lprobs.device
+    N = bsz * beam
+    if lprobs.dtype != torch.float32 or tuple(lprobs.shape) != (N, V) or not lprobs.is_contiguous():
+        raise ValueError(f"sample_step: lprobs must be contiguous fp32 [{N}, {V}], got {lprobs.dtype} "
+                         f"{tuple(lprobs.shape)}")
+    if ids.dtype != torch.int64 or tuple(ids.shape) != (bsz,) or ids.device != dev or not ids.is_contiguous():
+        raise ValueError(f"sample_step: ids must be contiguous int64 [{bsz}] on {dev}")
+    if not first_step and (prev_col is None or prev_col.dtype != torch.float32 or prev_col.numel() != N):
+        raise ValueError(f"sample_step: prev_col must be an fp32 column of {N} scores after the first step")
+    sc = torch.empty(bsz, beam, dtype=torch.float32, device=dev)
+    lp = torch.empty(bsz, beam, dtype=torch.float32, device=dev)
+    tok = torch.empty(bsz, beam, dtype=torch.int64, device=dev)
+    bm = torch.empty(bsz, beam, dtype=torch.int64, device=dev)
+    kept = torch.empty(bsz, beam, dtype=torch.int32, device=dev)
+    ld = prev_col.stride(0) if prev_col is not None else 0
+    call("mms2ut_sample_step", lprobs.data_ptr(), _p(prev_col), ld, ids.data_ptr(), bsz, beam, V, int(step),
+         int(first_step), int(seed) & 0xFFFFFFFFFFFFFFFF, int(topk) if topk > 0 else 0,
+         float(topp) if topp > 0 else 0.0, sc.data_ptr(), lp.data_ptr(), tok.data_ptr(), bm.data_ptr(),
+         kept.data_ptr(), _s())
+    return sc, tok, bm, lp, kept
+
+
 def kv_cache_gather(src, dst, idx, rows):
     """dst[l, n, :rows] = src[l, idx[n], :rows] for caches [L, N, maxT, width] (idx int64 on device)."""
     L, Ns, T, W = src.shape

@@ -279,12 +279,14 @@ class MultiModalSpeechToSpeechTask:
 
     def build_generator(self, models, args, **kw):
         """fairseq SpeechToSpeechTask.build_generator for unit targets: beam search
-        (--beam, --max-len-a, --max-len-b, --lenpen, --min-len; 2_inference.sh:34-44)."""
+        (--beam, --max-len-a, --max-len-b, --lenpen, --min-len; 2_inference.sh:34-44) with
+        fairseq-generate's search controls (--temperature, --unkpen, --no-repeat-ngram-size) or its
+        Sampling search (--sampling, --sampling-topk, --sampling-topp, --seed)."""
         return UnitSequenceGenerator(models, beam_size=getattr(args, "beam", 5),
                                      max_len_a=getattr(args, "max_len_a", 0.0),
                                      max_len_b=getattr(args, "max_len_b", 200),
                                      len_penalty=getattr(args, "lenpen", 1.0),
-                                     min_len=getattr(args, "min_len", 1))
+                                     min_len=getattr(args, "min_len", 1), **search_controls(args))
 
     def build_vocoder(self, args=None, device="cuda"):
         """The data config's ``vocoder: {type: code_hifigan, checkpoint, config}`` mapping (fairseq
@@ -309,19 +311,22 @@ class UnitSequenceGenerator:
     sorted by score: {"tokens", "score", "attention", "alignment", "positional_scores"}) over
     generate.IncrementalDecoder (HIP) + generate.SequenceGenerator."""
 
-    def __init__(self, models, beam_size=5, max_len_a=0.0, max_len_b=200, len_penalty=1.0, min_len=1):
+    def __init__(self, models, beam_size=5, max_len_a=0.0, max_len_b=200, len_penalty=1.0, min_len=1, **controls):
+        """``controls``: generate.generate's search keywords (``search_controls(args)``)."""
         if len(models) != 1:
             raise NotImplementedError("ensembles in beam search")
         self.model = models[0]
         self.beam_size, self.max_len_a, self.max_len_b = beam_size, max_len_a, max_len_b
         self.len_penalty, self.min_len = len_penalty, min_len
+        self.controls = controls
 
     def generate(self, models, sample, **kw):
         from . import generate as G
         net = (models[0] if models else self.model).net
         batch = runtime.prepare_batch(sample, net.cfg, net.device)
+        ids = sample.get("id") if self.controls.get("sampling") else None    # the sampling stream's key
         hyps = G.generate(net, batch, self.beam_size, self.max_len_a, self.max_len_b,
-                          len_penalty=self.len_penalty, min_len=self.min_len)
+                          len_penalty=self.len_penalty, min_len=self.min_len, sample_ids=ids, **self.controls)
         for hs in hyps:
             for h in hs:
                 h["attention"], h["alignment"] = None, None
@@ -723,12 +728,20 @@ def build_parser():
     p.add_argument("--max-len-b", type=int, default=200)
     p.add_argument("--lenpen", type=float, default=1.0)
     p.add_argument("--min-len", type=int, default=1)
+    p.add_argument("--temperature", type=float, default=1.0)
+    p.add_argument("--unkpen", type=float, default=0.0)
+    p.add_argument("--no-repeat-ngram-size", type=int, default=0)
+    p.add_argument("--sampling", action="store_true")
+    p.add_argument("--sampling-topk", type=int, default=-1)
+    p.add_argument("--sampling-topp", type=float, default=-1.0)
     return p
 
 
 # fairseq-generate's own defaults for the flags that belong to the run, not to the trained model:
 # they never come from the checkpoint's saved args
 GENERATE_DEFAULTS = {"beam": 5, "max_len_a": 0.0, "max_len_b": 200, "lenpen": 1.0, "min_len": 1, "nbest": 1,
+                     "temperature": 1.0, "unkpen": 0.0, "no_repeat_ngram_size": 0, "sampling": False,
+                     "sampling_topk": -1, "sampling_topp": -1.0,
                      "gen_subset": "test", "max_tokens": None, "results_path": None, "path": None,
                      "required_batch_size_multiple": 1, "skip_invalid_size_inputs_valid_test": False,
                      "noise_config_yaml": None, "user_dir": None, "vocoder": None, "fp16": False,
@@ -766,6 +779,13 @@ def build_generate_parser():
     p.add_argument("--lenpen", type=float)
     p.add_argument("--min-len", type=int)
     p.add_argument("--nbest", type=int)
+    p.add_argument("--temperature", type=float, help="divide the logits by this before the softmax (> 0)")
+    p.add_argument("--unkpen", type=float, help="subtracted from <unk>'s log-probability")
+    p.add_argument("--no-repeat-ngram-size", type=int, help="no hypothesis repeats an n-gram of this size")
+    p.add_argument("--sampling", action="store_true", help="sample hypotheses instead of beam search")
+    p.add_argument("--sampling-topk", type=int, help="sample from the K most likely tokens")
+    p.add_argument("--sampling-topp", type=float, help="sample from the smallest set of tokens whose "
+                                                       "probability reaches P")
     p.add_argument("--results-path")
     p.add_argument("--scoring", help="what the closing line reports over the best hypotheses: bleu (token BLEU4, "
                                      "the default) or wer")
@@ -798,4 +818,23 @@ def merge_generate_args(given, saved):
     args = argparse.Namespace(**out)
     if args.nbest < 1 or args.nbest > args.beam:
         raise SystemExit(f"mms2ut-generate: --nbest {args.nbest} must be in [1, --beam {args.beam}]")
+    if not args.temperature > 0:
+        raise SystemExit(f"mms2ut-generate: --temperature {args.temperature} must be greater than 0")
+    if args.no_repeat_ngram_size < 0 or args.no_repeat_ngram_size > 64:
+        raise SystemExit(f"mms2ut-generate: --no-repeat-ngram-size {args.no_repeat_ngram_size} must be in [0, 64]")
+    if args.sampling_topk > 0 and args.sampling_topp > 0:
+        raise SystemExit("mms2ut-generate: --sampling-topk and --sampling-topp exclude each other")
+    if (args.sampling_topk > 0 or args.sampling_topp > 0) and not args.sampling:
+        raise SystemExit("mms2ut-generate: --sampling-topk / --sampling-topp require --sampling")
+    if args.sampling and args.beam > 256:
+        raise SystemExit(f"mms2ut-generate: --sampling needs --beam <= 256, got {args.beam}")
     return args
+
+
+def search_controls(args):
+    """generate.generate's search keywords from a namespace carrying fairseq-generate's flags
+    (absent ones take fairseq's defaults)."""
+    return {"temperature": getattr(args, "temperature", 1.0), "unk_penalty": getattr(args, "unkpen", 0.0),
+            "no_repeat_ngram_size": getattr(args, "no_repeat_ngram_size", 0),
+            "sampling": getattr(args, "sampling", False), "sampling_topk": getattr(args, "sampling_topk", -1),
+            "sampling_topp": getattr(args, "sampling_topp", -1.0), "seed": getattr(args, "seed", 1) or 1}
